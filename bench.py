@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path particles -> P(k) on MI355X, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C4]
+    python bench.py [--gpus N --steps K --warmup W] [--config C4] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 starts its own N ranks (a `python -m torch.distributed.run` child, before
 this process touches the GPU) unless it already runs under a launcher (WORLD_SIZE set):
@@ -24,11 +24,14 @@ y passes, all-to-all (N > 1), x pass with fused |F|^2 shell binning, shell all-r
 the (nbins,) sums, P(k) table.  With N > 1 the SAME grid is slab-decomposed over the N GPUs
 (strong scaling, one RCCL all-to-all per scalar field).
 
-Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" explains every field).  Besides the timed
-region the default run also (a) runs the SAME step function on a small sample of the workload and
-compares its tables with the CPU oracle (`parity`), (b) times the oracle on that sample on one
-core and on all cores (`cpu_baseline`, `cpu_baseline_allcores`), (c) at N = 1 with the default
-config, times short runs of C2 and C3 (`other_configs`).
+Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" explains every field).  A plain run sets up,
+warms up, times the K steps and prints the headline (`value`, `ms_per_step`); `--dump-outputs DIR`
+writes the P(k) tables of the last timed step as DIR/<quantity>.npy.  With `--full` it also
+(a) takes per-kernel times, roofline and exchange figures from extra instrumented steps and checks
+the timed step's tables at full size, (b) runs the SAME step function on a small sample of the
+workload and compares its tables with the CPU oracle (`parity`), (c) times the oracle on that
+sample on one core and on all cores (`cpu_baseline`, `cpu_baseline_allcores`), (d) at N = 1 with
+the default config, times short runs of C2 and C3 (`other_configs`).
 """
 import argparse
 import json
@@ -55,9 +58,15 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C4", help="C1..C5 (vpower.synth.CONFIGS / WORKLOADS)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: roofline / per-kernel figures (instrumented extra steps), exchange diagnosis, "
+                         "full-size checks, standalone gridding, the other decomposition, oracle parity, C2 / C3, HBM probe, "
+                         "CPU baselines (the --no-* options and --profile-steps select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the P(k) tables of the last timed step as DIR/<quantity>.npy (nbins x 4: k, P(k), Psum, Nsample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short C2 / C3 runs of the default line")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the short C2 / C3 runs of the --full line")
     ap.add_argument("--no-full-check", action="store_true",
                     help="skip the full-size checks of the timed step's tables (exact shell counts, Parseval over all modes)")
     ap.add_argument("--unfused", action="store_true", help="NGP route: separate deposit and z-pass kernels (grid through HBM)")
@@ -76,7 +85,10 @@ def parse_args(argv=None):
                     help="launcher check: every rank joins a gloo group, all-reduces its rank and rank 0 prints "
                          "{'dry_run': true, 'n_gpus': N}; no GPU is touched")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="with --dry-run: this rank exits with code 3")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def dry_run(args):
@@ -464,8 +476,17 @@ def cpu_model():
 
 
 # ------------------------------------------------------------------------------------------------
-def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_steps, want_parity, want_cpu):
-    """Times one config; returns the result dict (rank 0 fills the CPU legs)."""
+def dump_tables(dump_dir, tabs):
+    """--dump-outputs: one (nbins, 4) table per quantity -- k, P(k), Psum, Nsample, what a spctrm() caller receives."""
+    os.makedirs(dump_dir, exist_ok=True)
+    for q, tab in tabs.items():
+        tab = np.asarray(tab)
+        np.save(os.path.join(dump_dir, q + ".npy"), tab if tab.dtype in (np.float32, np.float64) else tab.astype(np.float64))
+
+
+def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_steps, want_parity, want_cpu, dump_dir=None):
+    """Times one config; returns the result dict (rank 0 fills the CPU legs).  Without --full: set-up, warm-up, the timed
+    steps, the dump of the last timed step's tables, nothing more."""
     import torch
     import torch.distributed as dist
     from vpower import device, synth
@@ -492,8 +513,10 @@ def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_
     wl = Workload(K, comm, N, L, route, quantities, flavour, dpos, dvel, drho, unfused=args.unfused)
     nx = wl.nx
     nchunks = wl.pipe.nchunks
-    exchange_rows = None
-    if G > 1 and wl.pipe.chunked:
+    exchange_rows, wl_keep = None, None
+    if not args.full:       # (the row geometry below feeds the roofline and the exchange figures only)
+        pass
+    elif G > 1 and wl.pipe.chunked:
         # slot j of band c of a rank is plane c*G*nkc + j*G + rank (include/vps_hip.h: vps_fft_y): the rows this rank keeps,
         # and the share of a block's rows that crosses the node (the blocks leave the rows no shell can reach at home)
         nkc_ = N // 2 // G // nchunks
@@ -531,6 +554,40 @@ def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_
     ms_per_step = dt / steps * 1e3
     fw = getattr(comm, "field_world", 1)          # field-parallel ranks (device.FieldComm): G = 1, the FIELDS are dealt out
     cells = float(N) ** 3 * nfields * world / (G * fw)   # grid cells x scalar fields per step (whole job; emulation: one rank's share)
+    slab_run = wl.pipe.chunked and (G > 1 or bool(getattr(comm, "force", False)))
+    if dump_dir is not None and rank == 0:
+        dump_tables(dump_dir, tabs)
+    finite = all(np.isfinite(t[:, 2]).all() and t[:, 3].sum() > 0 for t in tabs.values())
+    if rank == 0 and not os.environ.get("VPS_BENCH_NOCHECK"):      # (timing-only kernel variants produce garbage)
+        assert finite, "non-finite shell sums"
+
+    def config_of(exchange):
+        bj = baseline_json()
+        idx = int(cfg[1]) - 1
+        cfg_text = bj["configs"][idx] if idx < len(bj.get("configs", [])) else cfg
+        return {"workload": "%s: %s" % (cfg, cfg_text),
+                "deviation": rehearsal or "; ".join(x for x in (
+                    ("strong-scaled over %d GPU(s) of one node" % world) if cfg in ("C4", "C5") and world != 8 else None,
+                    ("field-parallel decomposition (--decomposition fields) instead of the slab all-to-all the config names: every "
+                     "rank transforms whole grids and nothing but shell tables crosses xGMI; the slab run of the same step is timed "
+                     "under `alternative`") if fw > 1 else None) if x) or None,
+                "grid": N, "particles": Np, "route": route, "quantities": list(quantities),
+                "scalar_fields_per_step": nfields, "path": wl.describe_path(),
+                "decomposition": ("fields" if fw > 1 else "slab") if (world > 1 or G > 1 or slab_run) else "none (one GPU)",
+                **({"transport": ("libvps_hip.so: grouped ncclSend / ncclRecv on its own stream (RCCL)" if isinstance(comm, device.LibraryComm)
+                                  else "torch.distributed.all_to_all_single (%s)" % (backend if world > 1 else "emulated, no peers")),
+                    "chunks": nchunks, "chunks_in_flight": (2 if isinstance(comm, device.LibraryComm) else wl.pipe.inflight_max()),
+                    "exchange_row_fraction": exchange_rows, "slab_exchange": exchange,
+                    "ms_per_step_slab": ms_per_step} if slab_run else {}),
+                **({"ms_per_step_fields": ms_per_step} if fw > 1 else {}),
+                "parallelism": ("x-slab x%d, one message per field and pair of ranks in %d kz chunks (unbinned rows left out, Nyquist rows inside it)"
+                                % (world, nchunks)) if (G == world and world > 1)
+                else ("field-parallel: the step's %d scalar fields dealt out over %d ranks, whole %d^3 grid per GPU, only shell tables cross the node"
+                      % (nfields, fw, N)) if fw > 1
+                else "one GPU, no exchange" if G == world else ("EMULATED rank 0 of %d on one GPU, exchanges skipped (diagnostic)" % G)}
+
+    if not args.full:       # a plain run: the headline and nothing else (the buffers go with this frame)
+        return {"ms_per_step": ms_per_step, "value": cells * steps / dt, "config": config_of(None), "data": data}
 
     # ---- per-kernel durations (HIP events on the library's stream), untimed extra steps ----
     K.timing(True)
@@ -549,7 +606,6 @@ def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_
     #                        (nothing overlaps: exchange start -> arrival); library transport -- the grouped send / recv intervals
     #                        on the library's communication stream (VPS_K_EXCHANGE)
     exchange = None
-    slab_run = wl.pipe.chunked and (G > 1 or bool(getattr(comm, "force", False)))
     if slab_run:
         tsum = lambda name: tim.get(name, (0, 0.0))[1] / nst
         if isinstance(comm, device.LibraryComm):
@@ -622,32 +678,10 @@ def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_
     traffic, traffic_source = None, None
     if world == 1 and G == 1:
         traffic, traffic_source = pmc_traffic(cfg, dom)
-    bj = baseline_json()
-    idx = int(cfg[1]) - 1
-    cfg_text = bj["configs"][idx] if idx < len(bj.get("configs", [])) else cfg
     res = {
         "ms_per_step": ms_per_step,
         "value": cells * steps / dt,
-        "config": {"workload": "%s: %s" % (cfg, cfg_text),
-                   "deviation": rehearsal or "; ".join(x for x in (
-                       ("strong-scaled over %d GPU(s) of one node" % world) if cfg in ("C4", "C5") and world != 8 else None,
-                       ("field-parallel decomposition (--decomposition fields) instead of the slab all-to-all the config names: every "
-                        "rank transforms whole grids and nothing but shell tables crosses xGMI; the slab run of the same step is timed "
-                        "under `alternative`") if fw > 1 else None) if x) or None,
-                   "grid": N, "particles": Np, "route": route, "quantities": list(quantities),
-                   "scalar_fields_per_step": nfields, "path": wl.describe_path(),
-                   "decomposition": ("fields" if fw > 1 else "slab") if (world > 1 or G > 1 or slab_run) else "none (one GPU)",
-                   **({"transport": ("libvps_hip.so: grouped ncclSend / ncclRecv on its own stream (RCCL)" if isinstance(comm, device.LibraryComm)
-                                     else "torch.distributed.all_to_all_single (%s)" % (backend if world > 1 else "emulated, no peers")),
-                       "chunks": nchunks, "chunks_in_flight": (2 if isinstance(comm, device.LibraryComm) else wl.pipe.inflight_max()),
-                       "exchange_row_fraction": exchange_rows, "slab_exchange": exchange,
-                       "ms_per_step_slab": ms_per_step} if slab_run else {}),
-                   **({"ms_per_step_fields": ms_per_step} if fw > 1 else {}),
-                   "parallelism": ("x-slab x%d, one message per field and pair of ranks in %d kz chunks (unbinned rows left out, Nyquist rows inside it)"
-                                   % (world, nchunks)) if (G == world and world > 1)
-                   else ("field-parallel: the step's %d scalar fields dealt out over %d ranks, whole %d^3 grid per GPU, only shell tables cross the node"
-                         % (nfields, fw, N)) if fw > 1
-                   else "one GPU, no exchange" if G == world else ("EMULATED rank 0 of %d on one GPU, exchanges skipped (diagnostic)" % G)},
+        "config": config_of(exchange),
         "data": data,
         "particles_per_s": Np / (grid_ms * 1e-3) if grid_ms > 0 else None,
         "gridding_note": ("bucket sort only: the LDS accumulation of the fused path lives in the fft_z launch"
@@ -675,9 +709,6 @@ def run_config(args, cfg, K, comm, world, rank, backend, steps, warmup, profile_
         res["exchange_row_fraction"] = exchange_rows   # rows per kz plane in the exchanged blocks / N
     if exchange is not None:
         res["slab_exchange"] = exchange
-    finite = all(np.isfinite(t[:, 2]).all() and t[:, 3].sum() > 0 for t in tabs.values())
-    if rank == 0 and not os.environ.get("VPS_BENCH_NOCHECK"):      # (timing-only kernel variants produce garbage)
-        assert finite, "non-finite shell sums"
     # ---- the tables of the TIMED, full-size step itself: exact shell counts; Parseval over all modes (NGP routes) ----
     # (the oracle cannot follow at this size; these are the size-independent properties of SURVEY.md section 4, computed with
     # torch float64 as the calculator: oracle/gpu_checks.py.  What they exercise are the kernels that dominate the timed
@@ -1014,18 +1045,18 @@ def main(argv=None):
                          "(--emulate-ranks 8)" % (cfg, synth.CONFIGS[cfg][0]))
     res = run_config(args, cfg, K, comm, world, rank, backend, args.steps, args.warmup, args.profile_steps,
                      want_parity=not args.no_parity and (comm.world == world or getattr(comm, "field_world", 1) == world),
-                     want_cpu=single and not args.no_cpu_baseline)
+                     want_cpu=single and not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     out = {
         "metric": baseline_json()["metric"],
         "value_definition": "N^3 x scalar fields / step time: the whole path particles -> P(k) tables of the config's "
-                            "quantities; stage rates in particles_per_s and fft_cells_per_s, HBM fraction in roofline",
+                            "quantities; with --full, stage rates in particles_per_s and fft_cells_per_s, HBM fraction in roofline",
         "value": res.pop("value"), "unit": "grid cells*components/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": res.pop("ms_per_step"), "higher_is_better": True, "scaling": "strong",
         "vs_baseline": None, "dtype": "f32", "data": res.pop("data"),
     }
     out.update(res)
-    if single and cfg == "C4" and not args.no_other_configs:
+    if args.full and single and cfg == "C4" and not args.no_other_configs:
         # the two single-GPU configs of BASELINE.json, short runs, reported beside the headline
         other = {}
         for c in ("C2", "C3"):
@@ -1043,9 +1074,9 @@ def main(argv=None):
         out["device_memory"] = {"peak_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 2),
                                 "peak_reserved_GB": round(torch.cuda.max_memory_reserved() / 1e9, 2),
                                 "total_GB": round(total_b / 1e9, 2)}
-    if single and rank == 0:
+    if args.full and single and rank == 0:
         out["hbm_probe"] = hbm_probe(torch)
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if args.full and rank == 0 and single and not args.no_cpu_baseline:
         out.update(cpu_baseline_legs(cfg))
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -361,7 +361,7 @@ def test_bench_main_several_ranks_rehearsal(tmp_path, world, transport):
         env.update(VPS_BENCH_TRANSPORT="library", VPS_FORCE_COLLECTIVES="1")
     else:
         env.update(VPS_BENCH_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--no-other-configs", "--profile-steps", "1"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -1020,14 +1020,14 @@ def test_nn_resample_quantity_forms(K, N, Np):
                                        (["--config", "C3"], "64"), (["--config", "C5", "--emulate-ranks", "8"], "128"),
                                        (["--config", "C1"], "64"), (["--config", "C2"], "128"), (["--unfused", "--no-other-configs"], "64")])
 def test_bench_command_line_paths(argv, grid, monkeypatch, capsys):
-    """bench.py's own control flow on one GPU at a rehearsal size (VPS_BENCH_GRID): the default line with its parity and
+    """bench.py's own control flow on one GPU at a rehearsal size (VPS_BENCH_GRID): the --full line with its parity and
     full-size checks, one emulated rank's share, the NN config, C5's emulated share -- each must print ONE JSON line with the
     contract's keys (the checks inside assert parity themselves)."""
     import json
     import bench
     monkeypatch.setenv("VPS_BENCH_GRID", grid)
     monkeypatch.setenv("VPS_BENCH_PARTICLES", "200000")
-    bench.main(argv + ["--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    bench.main(argv + ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
     lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -1037,3 +1037,30 @@ def test_bench_command_line_paths(argv, grid, monkeypatch, capsys):
     assert d["n_gpus"] == 1 and d["value"] > 0 and "REHEARSAL" in d["config"]["deviation"]
     if "--emulate-ranks" not in argv:
         assert d["parity"]["nsample_equal"] and d["parity"]["psum_max_rel"] < 2e-5 and d["full_size_check"]["nsample_exact"]
+
+
+@pytest.mark.parametrize("cfg", ["C4", "C3"])
+def test_bench_plain_run_dumps_the_timed_tables(cfg, tmp_path, monkeypatch, capsys):
+    """A plain `bench.py` (no --full) prints the headline only, and --dump-outputs writes the last timed step's tables, which
+    are the oracle's tables of the same seeded particles."""
+    import json
+    import bench
+    from vpower import synth as vsynth
+    N, Np = 64, 200_000
+    monkeypatch.setenv("VPS_BENCH_GRID", str(N))
+    monkeypatch.setenv("VPS_BENCH_PARTICLES", str(Np))
+    bench.main(["--config", cfg, "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32" and d["higher_is_better"]
+    for key in ("roofline", "parity", "full_size_check", "other_configs", "cpu_baseline", "hbm_probe"):
+        assert key not in d
+    route, quantities, flavour = vsynth.WORKLOADS[cfg]
+    pos, vel, _, dens = vsynth.particles(vsynth.BASE_SEED + vsynth.CONFIGS[cfg][2], Np, 1.0, True)
+    ora, _ = bench.oracle_tables(route, quantities, flavour, N, 1.0, pos, vel, dens)
+    got = {q: np.load(tmp_path / (q + ".npy")) for q in quantities}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(q + ".npy" for q in quantities)
+    assert all(t.dtype == np.float64 and t.shape == np.asarray(ora[q]).shape for q, t in got.items())
+    eq, worst = bench.compare_tables(got, ora)
+    assert eq and worst <= PSUM_RTOL

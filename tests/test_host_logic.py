@@ -238,6 +238,17 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert r2.returncode == 2
 
 
+def test_bench_options():
+    """A plain bench run leaves the extra legs to --full; --steps is the number of timed steps, at least one."""
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out" and not a.full
+    assert bench.parse_args(["--full"]).full and bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 @pytest.mark.parametrize("n", [200_000, 1_000_000])
 def test_residency_fingerprint_sees_sparse_in_place_edits(n):
     """GasParticles keeps device copies keyed by a hash of EVERY byte of the host array (vpower/interp.py `_fingerprint`): the

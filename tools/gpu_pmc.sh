@@ -3,10 +3,11 @@
 # one rocprofv3 --pmc pass (counters only, no tracing) of a short bench run; prints, per kernel, the value of every
 # counter for the launch with the largest first counter (= the main launch of that kernel)
 tag=$1; ctrs=$2; shift 2
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out/prof
-rocprofv3 --pmc $ctrs --output-format csv -d gpurun_out/prof/${tag}_pmc -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-parity --no-other-configs --profile-steps 1 "$@" > gpurun_out/prof/${tag}_pmc.log 2>&1
-f=$(ls gpurun_out/prof/${tag}_pmc/*/*_counter_collection.csv | head -1)
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
+out=${VPS_PROF_DIR:-prof_out}     # where the artefacts go (kept out of git)
+mkdir -p "$out"
+rocprofv3 --pmc $ctrs --output-format csv -d $out/${tag}_pmc -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-parity --no-other-configs --profile-steps 1 "$@" > $out/${tag}_pmc.log 2>&1
+f=$(ls $out/${tag}_pmc/*/*_counter_collection.csv | head -1)
 python3 - "$f" $ctrs <<'PY'
 import csv,sys,re
 from collections import defaultdict
@@ -23,4 +24,4 @@ for d,c in disp.items():
 for n,c in sorted(best.items(), key=lambda kv:-kv[1].get(ctrs[0],0))[:12]:
     print("%-50s "%n+" ".join("%s=%.4g"%(k,c.get(k,float('nan'))) for k in ctrs))
 PY
-rm -rf gpurun_out/prof/${tag}_pmc
+rm -rf $out/${tag}_pmc
