@@ -368,7 +368,11 @@ int vps_fft_x_bin(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0,
                   double* psum_dev, unsigned long long* nsample_dev);
 /* Binning x pass of ONE received chunk of the slab exchange (layout: vps_fft_y): in_devs[c] = the G blocks this rank
  * received for component c, `packed` what the senders' vps_fft_y_packed() returned; count as in vps_fft_x_bin.  The last
- * chunk's Nyquist-plane rows are binned by the same call. */
+ * chunk's Nyquist-plane rows are binned by the same call.
+ * Rank-count limit: a received x line is G segments of nx = N / G points, and the x pass of the N = 1024, 2048, 4096 lines
+ * (64, 128, 256 lanes per line) needs segments of at least one point per lane -- at most 16 ranks at those sizes; every
+ * other N takes any G that divides N / 2.  More ranks: VPS_ERR_UNSUPPORTED at the entry of this call and of
+ * vps_spectrum_zimages, before anything is enqueued. */
 int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
                         const void* const* in_devs, int ncomp, int count, double* psum_dev,
                         unsigned long long* nsample_dev);
@@ -386,6 +390,7 @@ int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chu
  *                         first, so chunk c travels while c + 1 is transformed and is binned while c + 1 travels.  Needs the
  *                         tables of vps_set_binning; blocks carry only the rows a shell can reach.  Accumulates into
  *                         psum_dev / (count != 0) nsample_dev; xwork_dev: vps_spectrum_zimages_workspace_bytes.
+ *                         At most 16 ranks for N = 1024, 2048, 4096 (vps_fft_x_bin_chunk): refused before any enqueue.
  *   vps_allreduce_shells  sum of the accumulators over the ranks (ncclAllReduce, float64 + uint64), on the context's stream */
 int vps_comm_unique_id(char* id128);
 int vps_comm_create(vps_ctx* ctx, int rank, int world, const char* id128);

@@ -201,6 +201,10 @@ int vps_spectrum_zimages(vps_ctx* ctx, int N, int nx, const void* const* zimg_de
   if (nx * G != N) return vps_fail(ctx, VPS_ERR_ARG, "vps_spectrum_zimages: nx=%d x %d ranks != N=%d", nx, G, N);
   if (nchunks < 1 || vps_fft_y_chunk_elems(N, nx, G, nchunks, 0) < 0)
     return vps_fail(ctx, VPS_ERR_ARG, "vps_spectrum_zimages: %d ranks x %d chunks must divide N/2=%d", G, nchunks, N / 2);
+  // (the x pass's own refusal would come after the first chunks' y passes and exchanges have been enqueued)
+  if (G > vps_x_max_ranks(N))
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_spectrum_zimages: N=%d takes at most %d ranks (world=%d): the x pass needs segments "
+                    "of at least %d points", N, vps_x_max_ranks(N), G, N / vps_x_max_ranks(N));
   RcclApi& api = rccl();
   while ((int)cm->ev_y.size() < nchunks) {
     hipEvent_t a, b, c;

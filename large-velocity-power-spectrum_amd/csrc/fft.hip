@@ -2747,6 +2747,13 @@ int launch_transpose(vps_ctx* ctx, const PassParams& p, int kind) {
   return VPS_OK;
 }
 
+// Shortest segment the SEG x pass loads: power-of-two lines whose plan has a multiple of 64 lanes (N = 1024, 2048, 4096) carry
+// only the scalar-base load of load_line, which needs segments of at least L points; every other line takes any segment.
+template <int NC>
+constexpr int x_seg_min_len() {
+  return ((NC & (NC - 1)) == 0 && PlanInfo<NC>::L % 64 == 0) ? PlanInfo<NC>::L : 1;
+}
+
 template <int NC, int MODE, bool COUNT = false>
 int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 general shell walk, 1 mirrored kx (float64), 2 integer shells
   XParams p = p_in;
@@ -2760,8 +2767,9 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
                         (size_t)p.nbins * sizeof(double) + (COUNT ? (size_t)p.nbins * sizeof(unsigned) : 0) +
                         (p.win ? (size_t)NC * sizeof(float) : 0);
   if (lds > ctx->lds_per_cu) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "x pass needs %zu B LDS", lds);
-  if (seg && (NC & (NC - 1)) == 0 && PI::L % 64 == 0 && (p.seg_shift < 0 || p.seglen < PI::L))
-    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "x pass: lines of %d points in segments of %d (more than %d ranks)", NC, p.seglen, NC / PI::L);
+  if (seg && x_seg_min_len<NC>() > 1 && (p.seg_shift < 0 || p.seglen < x_seg_min_len<NC>()))   // (callers check vps_x_max_ranks first)
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "x pass: lines of %d points in segments of %d (more than %d ranks)", NC, p.seglen,
+                    NC / x_seg_min_len<NC>());
   auto kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 0> : fft_x_pass<NC, T, MODE, false, COUNT, 0>;
   if constexpr (MODE == 0 && NC >= 32) {
     if (fast == 1) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 1> : fft_x_pass<NC, T, MODE, false, COUNT, 1>;
@@ -3029,6 +3037,21 @@ void vps_fft_free_tables(vps_ctx* ctx) {
     (void)hipFree(kv.second.tw_r2c);
   }
   ctx->fft_tables.clear();
+}
+
+int vps_x_max_ranks(int N) {
+  switch (N) {
+    case 16: return 16 / x_seg_min_len<16>();
+    case 32: return 32 / x_seg_min_len<32>();
+    case 64: return 64 / x_seg_min_len<64>();
+    case 128: return 128 / x_seg_min_len<128>();
+    case 256: return 256 / x_seg_min_len<256>();
+    case 512: return 512 / x_seg_min_len<512>();
+    case 1024: return 1024 / x_seg_min_len<1024>();
+    case 2048: return 2048 / x_seg_min_len<2048>();
+    case 4096: return 4096 / x_seg_min_len<4096>();
+    default: return N;   // (x_seg_min_len is 1 for every other line length)
+  }
 }
 
 static int fft_y_of(vps_ctx* ctx, int N, int nx, const cf* B, const cf* BN, void* spec_dev, void* nyq_dev);
@@ -3446,6 +3469,9 @@ int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chu
   for (int c = 0; c < ncomp; ++c)
     if (!in_devs[c]) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_chunk: null component %d", c);
   if (nx < 1 || nx * G != N || rank < 0 || rank >= G) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_chunk: nx * G must be N, 0 <= rank < G");
+  if (G > vps_x_max_ranks(N))
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_fft_x_bin_chunk: N=%d takes at most %d ranks (G=%d): the x pass needs segments of at "
+                    "least %d points", N, vps_x_max_ranks(N), G, N / vps_x_max_ranks(N));
   const int2* tab = nullptr;
   long long rows = 0;
   int rc = ypack_get(ctx, N, G, nchunks, chunk, packed != 0, &tab, &rows);

@@ -121,6 +121,9 @@ struct vps_launch_timer {
 
 // fft.hip
 int vps_fft_get_tables(vps_ctx* ctx, int NC, vps_fft_tables* out);
+// most slab ranks G whose segmented x pass (segments of N / G points) exists for lines of N points: 16 for N = 1024, 2048,
+// 4096, else N (include/vps_hip.h: vps_fft_x_bin_chunk); an internal symbol, not part of the exported ABI
+__attribute__((visibility("hidden"))) int vps_x_max_ranks(int N);
 void vps_fft_free_tables(vps_ctx* ctx);
 // fused deposit -> z pass ("pencil" path): records sorted by pencil -> ncomp half spectra
 int vps_pencil_tp(int N);

@@ -77,6 +77,13 @@ def window_inv2_axis(Nsize, assignment):
     return (w ** (-2.0 * p)).astype(np.float32)
 
 
+def x_max_ranks(Nsize):
+    """Most slab ranks the binning x pass takes for N = Nsize (include/vps_hip.h: vps_fft_x_bin_chunk): a rank's segment of a
+    received x line has N / ranks points, and the lines of N = 1024, 2048 and 4096 (64, 128 and 256 lanes per line) need
+    segments of at least one point per lane -- 16 ranks.  Every other supported N takes any rank count that divides N / 2."""
+    return 16 if int(Nsize) in (1024, 2048, 4096) else int(Nsize)
+
+
 def sqrt_thresholds(edges):
     """thr[i] = smallest float64 t with sqrt(t) >= edges[i] (i < nbins) and
     thr[nbins] = smallest t with sqrt(t) > edges[nbins], so that comparing
@@ -867,6 +874,9 @@ class PowerPipeline:
             raise Exception("Nsize=%d is not supported by the device FFT (powers of two 16..4096, 96, 192, 384, 768, 1536, 250, 500, 1000, 2000)" % self.N)
         if self.N % G or (self.N // 2) % G:
             raise Exception("Nsize/2=%d must be divisible by the number of ranks %d" % (self.N // 2, G))
+        if G > x_max_ranks(self.N):    # refused here, before any exchange is enqueued: the x pass would refuse mid-pipeline
+            raise Exception("Nsize=%d takes at most %d ranks, not %d: the x pass needs segments of at least %d points per line"
+                            % (self.N, x_max_ranks(self.N), G, self.N // x_max_ranks(self.N)))
         self.nx = self.N // G
         self.x0 = self.comm.rank * self.nx
         self.flavour = flavour

@@ -360,3 +360,31 @@ def test_built_library_passed_the_pipeline_check():
     rep = json.load(open(_ffi.NN_CHECK_REPORT))
     assert rep["violations"] == 0 and rep["requests"] >= 75, rep       # 25 classes x 3 step bodies per instantiation
     assert rep["source_sha16"] == _ffi._source_sha(os.path.join(_ffi.CSRC, "nn.hip"))
+
+
+def test_pipeline_refuses_more_ranks_than_the_x_pass_takes():
+    """N = 1024, 2048, 4096 take at most 16 slab ranks (include/vps_hip.h: vps_fft_x_bin_chunk): PowerPipeline refuses more
+    when it is built, before any pass or exchange, with an error naming the limit; 16 ranks and other sizes are accepted."""
+    from vpower import device
+
+    class NoKernels:           # any call beyond the size query would be a pass enqueued
+        def fft_supported(self, N):
+            return True
+
+        def __getattr__(self, name):
+            raise AssertionError("PowerPipeline called %s while being refused" % name)
+
+    def comm(world):
+        c = device.SlabComm(enabled=False)
+        c.world, c.rank = world, world - 1
+        return c
+    for N in (1024, 2048, 4096):
+        assert device.x_max_ranks(N) == 16
+        pipe = device.PowerPipeline(N, 1.0, kernels=NoKernels(), comm=comm(16))
+        assert pipe.nx == N // 16 and pipe.chunked
+        for G in (32, 64):
+            with pytest.raises(Exception, match="at most 16 ranks, not %d" % G):
+                device.PowerPipeline(N, 1.0, kernels=NoKernels(), comm=comm(G))
+    for N, G in ((512, 32), (512, 256), (1536, 32), (2000, 40), (1000, 20), (256, 128)):
+        assert device.x_max_ranks(N) == N
+        assert device.PowerPipeline(N, 1.0, kernels=NoKernels(), comm=comm(G)).nx == N // G
