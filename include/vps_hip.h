@@ -74,7 +74,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 6
+#define VPS_ABI_VERSION 7
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -376,6 +376,22 @@ int vps_fft_x_bin(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0,
 int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
                         const void* const* in_devs, int ncomp, int count, double* psum_dev,
                         unsigned long long* nsample_dev);
+
+/* Helmholtz decomposition of a VECTOR field (ABI 7): vps_fft_x_bin / vps_fft_x_bin_chunk with the same arguments and one more
+ * float64 accumulator, psum_comp_dev[nbins], into which the COMPRESSIVE (curl-free) part of every mode is binned with the
+ * same shell decision, Hermitian multiplicity and window factor as its |F|^2:
+ *     |D|^2 / |k'|^2,  D = k'x Fx + k'y Fy + k'z Fz   (0 where k' = 0),
+ * k' = the integer mode numbers fftfreq(N) * N of each axis with the Nyquist entry N/2 set to 0 (odd under k -> -k, so that
+ * a mode and its Hermitian partner get the same projection).  psum_dev / nsample_dev take exactly what vps_fft_x_bin adds
+ * to them; the solenoidal part is psum_dev - psum_comp_dev (the axis-Nyquist modes, k' = 0, count as solenoidal).
+ * in_devs[0..2] are the x, y, z components (x = the line axis, y = the row, z = the halved axis); ncomp must be 3 (else
+ * VPS_ERR_ARG).  The chunk form has the rank-count limit of vps_fft_x_bin_chunk, refused at its entry. */
+int vps_fft_x_bin_helmholtz(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0,
+                            const void* const* in_devs, int ncomp, int nseg, int64_t seg_stride, int count,
+                            double* psum_dev, unsigned long long* nsample_dev, double* psum_comp_dev);
+int vps_fft_x_bin_chunk_helmholtz(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
+                                  const void* const* in_devs, int ncomp, int count, double* psum_dev,
+                                  unsigned long long* nsample_dev, double* psum_comp_dev);
 
 /* ---- slab exchange inside the library: RCCL over xGMI (one process per GPU) -------------------------------------------
  * For hosts without a collective of their own (the Python host drives the same chunk pipeline through torch.distributed,

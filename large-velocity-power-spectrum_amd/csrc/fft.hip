@@ -2108,6 +2108,9 @@ struct XParams {
   float kf;
   double* part_sum;    // [grid][nbins] per-workgroup partial shell sums
   unsigned* part_cnt;  // [grid][nbins] per-workgroup partial shell counts
+  // Helmholtz decomposition (HELM, ncomp = 3): shell sums of |k'.F|^2 / |k'|^2 (vps_fft_x_bin_helmholtz) and their partials
+  double* psumc;
+  double* part_sumc;
 };
 
 // FAST (MODE 0 only): the k^2 table is symmetric (k2[N-i] == k2[i]) and non-decreasing on
@@ -2131,30 +2134,43 @@ template <int NC, int FASTMODE, bool SEG>
 constexpr bool x_twreg() {
   return FASTMODE == 2 && NC == 2048 && PlanInfo<NC>::R2 > 1;
 }
-template <int NC, int T, int MODE, bool SEG, bool COUNT, int FASTMODE>
+// HELM (MODE 0, ncomp = 3): Helmholtz decomposition.  While the three components of a line are transformed one after the other,
+// D = k'x Fx + k'y Fy + k'z Fz (k' = integer mode numbers, the Nyquist entry N/2 of every axis set to 0) is accumulated in
+// registers; |D|^2 / |k'|^2 (0 where k' = 0) -- the compressive part of sum_c |F_c|^2 -- goes through a second LDS image next
+// to the |F|^2 image and is binned with the same shell decision into a second set of shell sums (p.psumc).
+// k' is odd under k -> -k, so a mode and its Hermitian partner have the same |D|^2: the half spectrum's multiplicities hold.
+template <int NC>
+constexpr int x_cimg_pitch(bool fast) {   // floats per line of the HELM image: index k + k / CH, k < NC
+  return NC + NC / (fast ? PlanInfo<NC>::RL / 2 : PlanInfo<NC>::RL) + 1;
+}
+template <int NC, int T, int MODE, bool SEG, bool COUNT, int FASTMODE, bool HELM = false>
 #ifndef VPS_X_MIN_WAVES
 #define VPS_X_MIN_WAVES 1
 #endif
-__global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG>() ? 3 : VPS_X_MIN_WAVES)) fft_x_pass(const XParams p) {
+__global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG>() ? (HELM ? 2 : 3) : VPS_X_MIN_WAVES)) fft_x_pass(const XParams p) {
   typedef PlanInfo<NC> PI;
   constexpr bool FAST = FASTMODE != 0, INTB = FASTMODE == 2, TWREG = x_twreg<NC, FASTMODE, SEG>();
   constexpr int L = PI::L, RL = PI::RL, NT = T * L;
   constexpr int H = RL / 2;   // |kx| values per lane on the FAST path
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  // carve: thr (double, nbins+2 with a +inf sentinel; INTB: unsigned, 0xffffffff sentinel) | hsum (double) | tw | line buffers | hcnt
+  // carve: thr (double, nbins+2 with a +inf sentinel; INTB: unsigned, 0xffffffff sentinel) | hsum (double) | [HELM: hsumc (double)]
+  //        | tw | line buffers | hcnt | [window factors] | [HELM: T images of |D|^2 / |k'|^2]
   double* thr = reinterpret_cast<double*>(smem_raw);
   unsigned* nthr = reinterpret_cast<unsigned*>(smem_raw);
   double* hsum = INTB ? reinterpret_cast<double*>(nthr + ((p.nbins + 3) & ~1)) : thr + (MODE == 0 ? (p.nbins + 2) : 0);
-  cf* tw_lds = reinterpret_cast<cf*>(hsum + (MODE == 0 ? p.nbins : 0));
+  double* hsumc = hsum + p.nbins;   // (HELM only)
+  cf* tw_lds = reinterpret_cast<cf*>(hsum + (MODE == 0 ? p.nbins : 0) + (HELM ? p.nbins : 0));
   constexpr int TWCOPY = TWREG ? PI::TW1 : PI::TW;                      // twiddle entries staged in LDS
   constexpr int TWRES = TWREG ? ((PI::TW1 + 1) & ~1) : PI::TWL;         // ... and reserved for them
   cf* buf = tw_lds + TWRES;
   const cf* tw = PI::TWLDS ? tw_lds : p.tw_stage;
   unsigned* hcnt = reinterpret_cast<unsigned*>(buf + T * PI::PITCH);
   float* wl = reinterpret_cast<float*>(hcnt + ((MODE == 0 && COUNT) ? p.nbins : 0));   // [NC] window factors (MODE 0 with p.win)
+  constexpr int CIMG = x_cimg_pitch<NC>(FAST);
 
   const int tid = threadIdx.x;
   const int t = tid / L, l = tid % L;
+  float* cimg = wl + (p.win ? NC : 0) + (HELM ? t * CIMG : 0);   // HELM: this line's |D|^2 / |k'|^2 image
   if constexpr (PI::TWLDS)
     for (int i = tid; i < TWCOPY; i += NT) tw_lds[i] = p.tw_stage[i];
   cf twr[TWREG ? (PI::R2 - 1) : 1];
@@ -2171,6 +2187,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
     }
     for (int i = tid; i < p.nbins; i += NT) {
       hsum[i] = 0.0;
+      if constexpr (HELM) hsumc[i] = 0.0;
       if constexpr (COUNT) hcnt[i] = 0u;
     }
     if (p.win)
@@ -2209,6 +2226,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
   double k2y = 0.0, k2z = 0.0;   // fl(ky*ky), fl(kz*kz) of the line (MODE 0)
   unsigned nyz = 0u;             // INTB: iy^2 + iz^2 of the line
   float wyz = 1.f;               // window factor of the line's (ky, kz)
+  float kyp = 0.f, kzp = 0.f;    // HELM: k'y, k'z of the line
   unsigned wz = 1u;              // Hermitian multiplicity of its kz plane
   double k2half = 0.0;
   if constexpr (MODE == 0 && !INTB) k2half = p.k2[NC / 2];
@@ -2273,6 +2291,11 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
         }
         wz = (kz == 0 || 2 * kz == NC) ? 1u : 2u;
         if (p.win) wyz = p.win[(int)(g % NC)] * p.win[kz];
+        if constexpr (HELM) {
+          const int kyi = (int)(g % NC);
+          kyp = (2 * kyi < NC) ? (float)kyi : (2 * kyi == NC ? 0.f : (float)(kyi - NC));
+          kzp = (2 * kz == NC) ? 0.f : (float)kz;
+        }
       }
     }
   };
@@ -2378,6 +2401,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
     const unsigned nyz_cur = nyz;
     const unsigned wz_cur = wz;
     const float wyz_cur = wyz;
+    const float kyp_cur = kyp, kzp_cur = kzp;
     if constexpr (MODE != 0) {
       exchange_sync<WSYNC>();  // previous tile's readers are done with the line buffers
       fft_from_regs<NC, WSYNC, (TWREG ? 2 : 0)>(v, line, tw, l, twr);
@@ -2409,6 +2433,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
       // squared its registers take the next loads: the next component of this tile, or the first of
       // the next tile, which then fly while this tile is binned.
       float pacc[RL];
+      float dre[HELM ? RL : 1], dim[HELM ? RL : 1];   // HELM: D = sum_c k'_c F_c of this lane's elements
       for (int c = 0; c < p.ncomp; ++c) {
         // opaque copy of the lane index: keeps the LDS / global addresses of this loop from being
         // hoisted out of it as ~50 extra live registers (an occupancy step)
@@ -2434,6 +2459,20 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
         for (int i = 0; i < RL; ++i) {
           const float a = v[i].x * v[i].x + v[i].y * v[i].y;
           pacc[i] = (c == 0) ? a : pacc[i] + a;
+        }
+        if constexpr (HELM) {
+#pragma unroll
+          for (int i = 0; i < RL; ++i) {
+            float kc;
+            if (c == 0) {
+              const int kx = out_index<NC>(lc, i);
+              kc = (2 * kx < NC) ? (float)kx : (2 * kx == NC ? 0.f : (float)(kx - NC));
+            } else {
+              kc = (c == 1) ? kyp_cur : kzp_cur;
+            }
+            dre[i] = (c == 0) ? kc * v[i].x : fmaf(kc, v[i].x, dre[i]);
+            dim[i] = (c == 0) ? kc * v[i].y : fmaf(kc, v[i].y, dim[i]);
+          }
         }
 #ifdef VPS_X_PREFETCH
 #pragma unroll
@@ -2469,6 +2508,14 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
           } else {
             const int k = out_index<NC>(lw, i);
             pw[k + k / CH] = pacc[i];
+          }
+          if constexpr (HELM) {
+            // |D|^2 / |k'|^2 into the line's second image, same index (every k' component an integer < 2^12: exact in float)
+            const int k = out_index<NC>(lw, i);
+            const float kx = (2 * k < NC) ? (float)k : (2 * k == NC ? 0.f : (float)(k - NC));
+            const float k2 = fmaf(kx, kx, fmaf(kyp_cur, kyp_cur, kzp_cur * kzp_cur));
+            const float d2 = fmaf(dre[i], dre[i], dim[i] * dim[i]);
+            cimg[k + k / CH] = (k2 > 0.f) ? d2 / k2 : 0.f;
           }
         }
       }
@@ -2514,6 +2561,20 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
               if (partner_cur) pv += mirr[POFF + 1];
               c = 2u;
             }
+            float pc = 0.f;   // HELM: the same modes of the |D|^2 / |k'|^2 images
+            if constexpr (HELM) {
+              const float* cm = cimg + l * (H + 1);
+              const float* cr = cimg + (NC + NC / H - 1) - l * (H + 1);
+              pc = cm[i];
+              if (partner_cur) pc += cm[i + CIMG];
+              if (i > 0) {
+                pc += cr[-i];
+                if (partner_cur) pc += cr[CIMG - i];
+              } else if (l > 0) {
+                pc += cr[1];
+                if (partner_cur) pc += cr[CIMG + 1];
+              }
+            }
 #ifdef VPS_ABL_X_NOATOMIC
             if ((unsigned)bin < (unsigned)p.nbins && pv == 1.2345e30f) {   // TIMING ONLY
 #else
@@ -2521,6 +2582,10 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
 #endif
               if (p.win) pv *= wl[l * H + i];
               atomicAdd(&hsum[bin], (double)(pv * wf));
+              if constexpr (HELM) {
+                if (p.win) pc *= wl[l * H + i];
+                atomicAdd(&hsumc[bin], (double)(pc * wf));
+              }
               if constexpr (COUNT) atomicAdd(&hcnt[bin], c * w);
             }
           };
@@ -2546,6 +2611,12 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
               if (partner_cur) pv += pw[NC / 2 + L + POFF];
               if (p.win) pv *= wl[NC / 2];
               atomicAdd(&hsum[bin], (double)(pv * wf));
+              if constexpr (HELM) {
+                float pc = cimg[NC / 2 + L];
+                if (partner_cur) pc += cimg[NC / 2 + L + CIMG];
+                if (p.win) pc *= wl[NC / 2];
+                atomicAdd(&hsumc[bin], (double)(pc * wf));
+              }
               if constexpr (COUNT) atomicAdd(&hcnt[bin], w);
             }
           }
@@ -2568,14 +2639,17 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
         else if (s >= thr[cur + 1]) cur = p.nbins;
         double hi = (cur < p.nbins) ? thr[cur + 1] : INFINITY;
         double lo = (cur >= 0) ? thr[cur] : -INFINITY;
-        double acc = 0.0;
+        double acc = 0.0, accc = 0.0;
         unsigned cnt = 0;
+        const float* minec = cimg + l * (RL + 1) + (rev ? RL - 1 : 0);   // (HELM)
         auto flush = [&]() {   // one LDS atomic per (lane, shell) run
           if (cur >= 0 && cur < p.nbins) {
             atomicAdd(&hsum[cur], acc * wd);
+            if constexpr (HELM) atomicAdd(&hsumc[cur], accc * wd);
             if constexpr (COUNT) atomicAdd(&hcnt[cur], cnt * w);
           }
           acc = 0.0;
+          if constexpr (HELM) accc = 0.0;
           cnt = 0;
         };
 #pragma unroll
@@ -2595,6 +2669,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
             lo = (cur >= 0) ? thr[cur] : -INFINITY;
           }
           acc += (double)(p.win ? mine[i * step] * wl[kx0 + i * step] : mine[i * step]);
+          if constexpr (HELM) accc += (double)(p.win ? minec[i * step] * wl[kx0 + i * step] : minec[i * step]);
           ++cnt;
         }
         flush();
@@ -2616,6 +2691,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
     unsigned* pc = p.part_cnt + (size_t)blockIdx.x * p.nbins;
     for (int i = tid; i < p.nbins; i += NT) {
       ps[i] = hsum[i];
+      if constexpr (HELM) p.part_sumc[(size_t)blockIdx.x * p.nbins + i] = hsumc[i];
       if constexpr (COUNT) pc[i] = hcnt[i];
     }
   }
@@ -2754,8 +2830,9 @@ constexpr int x_seg_min_len() {
   return ((NC & (NC - 1)) == 0 && PlanInfo<NC>::L % 64 == 0) ? PlanInfo<NC>::L : 1;
 }
 
-template <int NC, int MODE, bool COUNT = false>
+template <int NC, int MODE, bool COUNT = false, bool HELM = false>
 int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 general shell walk, 1 mirrored kx (float64), 2 integer shells
+  static_assert(!HELM || MODE == 0, "the Helmholtz decomposition is a binning variant");
   XParams p = p_in;
   constexpr int T = xpass_T<NC>();
   typedef PlanInfo<NC> PI;
@@ -2766,14 +2843,15 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
   if (MODE == 0) lds += (fast == 2 ? (size_t)((p.nbins + 3) & ~1) * sizeof(unsigned) : (size_t)(p.nbins + 2) * sizeof(double)) +
                         (size_t)p.nbins * sizeof(double) + (COUNT ? (size_t)p.nbins * sizeof(unsigned) : 0) +
                         (p.win ? (size_t)NC * sizeof(float) : 0);
+  if (HELM) lds += (size_t)p.nbins * sizeof(double) + (size_t)T * x_cimg_pitch<NC>(fast != 0) * sizeof(float);
   if (lds > ctx->lds_per_cu) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "x pass needs %zu B LDS", lds);
   if (seg && x_seg_min_len<NC>() > 1 && (p.seg_shift < 0 || p.seglen < x_seg_min_len<NC>()))   // (callers check vps_x_max_ranks first)
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "x pass: lines of %d points in segments of %d (more than %d ranks)", NC, p.seglen,
                     NC / x_seg_min_len<NC>());
-  auto kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 0> : fft_x_pass<NC, T, MODE, false, COUNT, 0>;
+  auto kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 0, HELM> : fft_x_pass<NC, T, MODE, false, COUNT, 0, HELM>;
   if constexpr (MODE == 0 && NC >= 32) {
-    if (fast == 1) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 1> : fft_x_pass<NC, T, MODE, false, COUNT, 1>;
-    if (fast == 2) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 2> : fft_x_pass<NC, T, MODE, false, COUNT, 2>;
+    if (fast == 1) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 1, HELM> : fft_x_pass<NC, T, MODE, false, COUNT, 1, HELM>;
+    if (fast == 2) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 2, HELM> : fft_x_pass<NC, T, MODE, false, COUNT, 2, HELM>;
   }
   if (lds > 64 * 1024)
     VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -2790,7 +2868,7 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
   if (grid > ntiles) grid = ntiles;
   if (grid < 1) return VPS_OK;
   if (MODE == 0) {
-    const size_t need = (size_t)grid * p.nbins * (sizeof(double) + sizeof(unsigned));
+    const size_t need = (size_t)grid * p.nbins * ((HELM ? 2 : 1) * sizeof(double) + sizeof(unsigned));
     if (need > ctx->xpart_cap) {
       VPS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
       if (ctx->d_xpart) VPS_HIP_CHECK(ctx, hipFree(ctx->d_xpart));
@@ -2800,7 +2878,8 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
       ctx->xpart_cap = need;
     }
     p.part_sum = reinterpret_cast<double*>(ctx->d_xpart);
-    p.part_cnt = reinterpret_cast<unsigned*>(p.part_sum + (size_t)grid * p.nbins);
+    p.part_sumc = HELM ? p.part_sum + (size_t)grid * p.nbins : nullptr;
+    p.part_cnt = reinterpret_cast<unsigned*>(p.part_sum + (size_t)grid * p.nbins * (HELM ? 2 : 1));
   }
   {
     vps_launch_timer tm(ctx, VPS_K_FFT_X);
@@ -2809,6 +2888,9 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
       hipLaunchKernelGGL(reduce_partials, dim3((unsigned)((p.nbins + 255) / 256), grid >= 64 ? 32u : 1u),
                          dim3(256), 0, ctx->stream,
                          p.part_sum, COUNT ? p.part_cnt : nullptr, (int)grid, p.nbins, p.psum, p.nsample);
+    if (HELM)
+      hipLaunchKernelGGL(reduce_partials, dim3((unsigned)((p.nbins + 255) / 256), grid >= 64 ? 32u : 1u),
+                         dim3(256), 0, ctx->stream, p.part_sumc, nullptr, (int)grid, p.nbins, p.psumc, nullptr);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;
@@ -2926,10 +3008,16 @@ int VPS_PARTFN(vps_fftpart_transpose)(vps_ctx* ctx, int NC, int real, const void
   return rc;
 }
 
-int VPS_PARTFN(vps_fftpart_x)(vps_ctx* ctx, int NC, int mode, int count, const void* params, int fast) {
+int VPS_PARTFN(vps_fftpart_x)(vps_ctx* ctx, int NC, int mode, int count, const void* params, int fast, int helm) {
   const XParams& p = *static_cast<const XParams*>(params);
   int rc = VPS_OK;
-  if (mode == 0 && count) {
+  if (helm) {   // (binning only: fft_x_impl checks)
+    if (count) {
+      VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, true, true>(ctx, p, fast)));
+    } else {
+      VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, false, true>(ctx, p, fast)));
+    }
+  } else if (mode == 0 && count) {
     VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, true>(ctx, p, fast)));
   } else if (mode == 0) {
     VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, false>(ctx, p, fast)));
@@ -2966,7 +3054,7 @@ int VPS_PARTFN(vps_fftpart_pencil)(vps_ctx* ctx, int NC, const void* params, lon
 #define VPS_DECL_PART(sfx)                                                                         \
   int VPS_CAT(vps_fftpart_tw, sfx)(int, std::vector<cf>*);                                          \
   int VPS_CAT(vps_fftpart_transpose, sfx)(vps_ctx*, int, int, const void*, int);                    \
-  int VPS_CAT(vps_fftpart_x, sfx)(vps_ctx*, int, int, int, const void*, int);                       \
+  int VPS_CAT(vps_fftpart_x, sfx)(vps_ctx*, int, int, int, const void*, int, int);                  \
   long long VPS_CAT(vps_fftpart_pencil_lds, sfx)(int);                                              \
   int VPS_CAT(vps_fftpart_pencil, sfx)(vps_ctx*, int, const void*, long long);
 VPS_FOR_PARTS(VPS_DECL_PART)
@@ -2985,9 +3073,9 @@ static int route_transpose(vps_ctx* ctx, int NC, int real, const PassParams& p, 
 #undef VPS_TRY
   return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "unsupported FFT length %d", NC);
 }
-static int route_x(vps_ctx* ctx, int NC, int mode, int count, const XParams& p, int fast) {
+static int route_x(vps_ctx* ctx, int NC, int mode, int count, const XParams& p, int fast, int helm = 0) {
   int rc;
-#define VPS_TRY(sfx) if ((rc = VPS_CAT(vps_fftpart_x, sfx)(ctx, NC, mode, count, &p, fast)) != VPS_PART_NOT_MINE) return rc;
+#define VPS_TRY(sfx) if ((rc = VPS_CAT(vps_fftpart_x, sfx)(ctx, NC, mode, count, &p, fast, helm)) != VPS_PART_NOT_MINE) return rc;
   VPS_FOR_PARTS(VPS_TRY)
 #undef VPS_TRY
   return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "unsupported FFT length %d", NC);
@@ -3373,7 +3461,7 @@ extern "C" {
 static int fft_x_impl(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0, const void* in_dev,
                       const void* in1_dev, const void* in2_dev, int ncomp, int nseg, int64_t seg_stride,
                       int mode, double* psum_dev, unsigned long long* nsample_dev, void* out_dev,
-                      const int2* ptab = nullptr, int kz_step = 1) {
+                      const int2* ptab = nullptr, int kz_step = 1, double* psumc_dev = nullptr) {
   VPS_ENTER(ctx);
   if (!vps_fft_supported(N)) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "N=%d: need a power of two in [16,4096], 96, 192, 384, 768, 1536, 250, 500, 1000 or 2000", N);
   if (nlines < 0 || !in_dev) return vps_fail(ctx, VPS_ERR_ARG, "bad line count / null input");
@@ -3421,10 +3509,12 @@ static int fft_x_impl(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz
     p.nmax = ctx->bin_nmax;
     p.kf = ctx->bin_kf;
     const int fastmode = !ctx->bin_fast ? 0 : (ctx->bin_int && ctx->d_nthr && vps_option("no_int_binning", 0) == 0) ? 2 : 1;
+    p.psumc = psumc_dev;
+    if (psumc_dev && ncomp != 3) return vps_fail(ctx, VPS_ERR_ARG, "Helmholtz decomposition: ncomp must be 3");
     if (mode == 0) {
-      rc = route_x(ctx, N, 0, 1, p, fastmode);
+      rc = route_x(ctx, N, 0, 1, p, fastmode, psumc_dev ? 1 : 0);
     } else {
-      rc = route_x(ctx, N, 0, 0, p, fastmode);
+      rc = route_x(ctx, N, 0, 0, p, fastmode, psumc_dev ? 1 : 0);
     }
   } else if (mode == 1) {
     if (!out_dev) return vps_fail(ctx, VPS_ERR_ARG, "null output");
@@ -3461,10 +3551,9 @@ int vps_fft_x_bin(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0, c
 // Binning x pass of ONE received chunk of the slab exchange: in_devs[c] = the G blocks this rank received for component c
 // (vps_fft_y's layout, x running over the senders' slabs), `packed` as the senders' vps_fft_y_packed said.  Planes of slot j
 // are kz = chunk*G*nkc + j*G + rank; the last chunk's blocks end with this rank's Nyquist-plane rows, binned here too.
-int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
-                        const void* const* in_devs, int ncomp, int count, double* psum_dev,
-                        unsigned long long* nsample_dev) {
-  VPS_ENTER(ctx);
+static int fft_x_bin_chunk_impl(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
+                                const void* const* in_devs, int ncomp, int count, double* psum_dev,
+                                unsigned long long* nsample_dev, double* psumc_dev) {
   if (ncomp < 1 || ncomp > 3 || !in_devs) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_chunk: ncomp must be 1..3");
   for (int c = 0; c < ncomp; ++c)
     if (!in_devs[c]) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_chunk: null component %d", c);
@@ -3481,12 +3570,42 @@ int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chu
   const long long blk = rows * nx + (last ? (long long)nky * nx : 0);
   const int mode = count ? 0 : 3;
   rc = fft_x_impl(ctx, N, (int64_t)nkc * N, 0, chunk * G * nkc + rank, in_devs[0], in_devs[ncomp > 1 ? 1 : 0],
-                  in_devs[ncomp > 2 ? 2 : 0], ncomp, G, blk, mode, psum_dev, nsample_dev, nullptr, tab, G);
+                  in_devs[ncomp > 2 ? 2 : 0], ncomp, G, blk, mode, psum_dev, nsample_dev, nullptr, tab, G, psumc_dev);
   if (rc || !last) return rc;
   const cf* nq[3];
   for (int c = 0; c < 3; ++c) nq[c] = reinterpret_cast<const cf*>(in_devs[c < ncomp ? c : 0]) + rows * nx;
   return fft_x_impl(ctx, N, nky, (int64_t)rank * nky, N / 2, nq[0], nq[1], nq[2], ncomp, G, blk, mode, psum_dev, nsample_dev,
-                    nullptr);
+                    nullptr, nullptr, 1, psumc_dev);
+}
+
+int vps_fft_x_bin_chunk(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
+                        const void* const* in_devs, int ncomp, int count, double* psum_dev,
+                        unsigned long long* nsample_dev) {
+  VPS_ENTER(ctx);
+  return fft_x_bin_chunk_impl(ctx, N, nx, G, nchunks, chunk, rank, packed, in_devs, ncomp, count, psum_dev, nsample_dev, nullptr);
+}
+
+// Helmholtz decomposition (include/vps_hip.h): the binning x passes above with a second accumulator of the compressive part
+int vps_fft_x_bin_helmholtz(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0, const void* const* in_devs,
+                            int ncomp, int nseg, int64_t seg_stride, int count, double* psum_dev,
+                            unsigned long long* nsample_dev, double* psum_comp_dev) {
+  VPS_ENTER(ctx);
+  if (ncomp != 3 || !in_devs) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_helmholtz: ncomp must be 3");
+  for (int c = 0; c < 3; ++c)
+    if (!in_devs[c]) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_helmholtz: null component %d", c);
+  if (!psum_comp_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_helmholtz: null compressive accumulator");
+  return fft_x_impl(ctx, N, nlines, line0, kz0, in_devs[0], in_devs[1], in_devs[2], 3, nseg, seg_stride, count ? 0 : 3,
+                    psum_dev, nsample_dev, nullptr, nullptr, 1, psum_comp_dev);
+}
+
+int vps_fft_x_bin_chunk_helmholtz(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int rank, int packed,
+                                  const void* const* in_devs, int ncomp, int count, double* psum_dev,
+                                  unsigned long long* nsample_dev, double* psum_comp_dev) {
+  VPS_ENTER(ctx);
+  if (ncomp != 3 || !in_devs) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_chunk_helmholtz: ncomp must be 3");
+  if (!psum_comp_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_x_bin_chunk_helmholtz: null compressive accumulator");
+  return fft_x_bin_chunk_impl(ctx, N, nx, G, nchunks, chunk, rank, packed, in_devs, 3, count, psum_dev, nsample_dev,
+                              psum_comp_dev);
 }
 
 int vps_power_bin(vps_ctx* ctx, int N, const float* field_dev, void* work_dev, double* psum_dev,

@@ -42,6 +42,9 @@ def build_parser():
     p.add_argument("-l", "--ltot", nargs="?", type=int, default=LTOT, help="Total length of the box.")
     p.add_argument("-b", "--nbuffer", nargs="?", type=int, default=NBUFFER, help="Accepted for compatibility; unused.")
     p.add_argument("-f", action="store_true", help="Skip confirmation and start the computation.")
+    p.add_argument("--helmholtz", action="store_true",
+                   help="Also write the compressive and solenoidal parts of the spectrum (Helmholtz decomposition) to "
+                        "Pk_compressive.txt and Pk_solenoidal.txt, in Pk.txt's format.")
     return p
 
 
@@ -110,10 +113,20 @@ def load_particles(path):
         return (f["PartType0/Coordinates"][:], f["PartType0/Masses"][:], f["PartType0/Velocities"][:])
 
 
-def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=None):
+def _script_table(tab):
+    tab[:, 1] *= 4 * np.pi * tab[:, 0] ** 2
+    tab = np.array(tab, dtype=np.float32)                       # :436
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        tab[:, 1] = tab[:, 2] / tab[:, 3] * (4 * np.pi * tab[:, 0] ** 2)   # :463
+    return tab
+
+
+def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=None, helmholtz=False):
     """The body of main() after loading: preprocessing, exact NN at x=i*LCELL (float32
     lattice, :343-346), raw velocity gather (:351), P(k) (:409-463).  Returns the float32
-    (nbins,4) table that rank 0 saves."""
+    (nbins,4) table that rank 0 saves; helmholtz=True: the tuple (total, compressive, solenoidal) of such tables
+    (vpower.device.PowerPipeline.accumulate_helmholtz; total is the table of helmholtz=False)."""
     import torch
     from vpower import device
     k = kernels if kernels is not None else device.default_kernels()
@@ -128,14 +141,11 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
     # Annoy holds float32 coordinates (add_item, :308): search them as float32
     pos = pos.to(torch.float32)
     grid, _ = k.nn_resample(pos, vel, (ax, ax, ax), pipe.x0, pipe.nx)
+    if helmholtz:
+        tabs = pipe.finish_helmholtz(*pipe.accumulate_helmholtz([grid[0], grid[1], grid[2]]))
+        return tuple(_script_table(t) for t in tabs)
     psum, ns = pipe.accumulate([grid[0], grid[1], grid[2]])
-    tab = pipe.finish(psum, ns)
-    tab[:, 1] *= 4 * np.pi * tab[:, 0] ** 2
-    tab = np.array(tab, dtype=np.float32)                       # :436
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        tab[:, 1] = tab[:, 2] / tab[:, 3] * (4 * np.pi * tab[:, 0] ** 2)   # :463
-    return tab
+    return _script_table(pipe.finish(psum, ns))
 
 
 def main(argv=None):
@@ -175,8 +185,13 @@ def main(argv=None):
         return 0
     print(f"[{datetime.datetime.now()}] Load snapshot: {args.input}", flush=True) if rank == 0 else None
     coords, mass, velocity = load_particles(args.input)
-    tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot)
+    tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot, helmholtz=args.helmholtz)
     if rank == 0:
+        if args.helmholtz:
+            tab, comp, sol = tab
+            for name, t in (("Pk_compressive.txt", comp), ("Pk_solenoidal.txt", sol)):
+                np.savetxt(os.path.join(args.output, name), t)
+                print(f"[{datetime.datetime.now()}] Saved: {os.path.join(args.output, name)}", flush=True)
         np.savetxt(outputfile, tab)
         print(f"[{datetime.datetime.now()}] Saved: {outputfile}", flush=True)
     if world > 1:

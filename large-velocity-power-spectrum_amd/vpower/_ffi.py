@@ -91,6 +91,10 @@ SYMBOLS = (
                                _vp, _vp)),
     ("vps_fft_x_bin_chunk", C.c_int, (_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp),
                                      C.c_int, C.c_int, _vp, _vp)),
+    ("vps_fft_x_bin_helmholtz", C.c_int, (_vp, C.c_int, _i64, _i64, C.c_int, C.POINTER(_vp), C.c_int, C.c_int, _i64, C.c_int,
+                                          _vp, _vp, _vp)),
+    ("vps_fft_x_bin_chunk_helmholtz", C.c_int, (_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(_vp), C.c_int, C.c_int, _vp, _vp, _vp)),
     ("vps_comm_unique_id", C.c_int, (C.c_char_p,)),
     ("vps_comm_create", C.c_int, (_vp, C.c_int, C.c_int, C.c_char_p)),
     ("vps_comm_destroy", C.c_int, (_vp,)),
@@ -112,7 +116,7 @@ KERNEL_KINDS = {"deposit": K_DEPOSIT, "algebra": K_ALGEBRA, "fft_z": K_FFT_Z, "f
                 "exchange": K_EXCHANGE, "exchange_wait": K_EXCHANGE_WAIT}
 
 
-ABI_VERSION = 6   # include/vps_hip.h: VPS_ABI_VERSION
+ABI_VERSION = 7   # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

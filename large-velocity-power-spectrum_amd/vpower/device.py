@@ -621,6 +621,25 @@ class HipKernels:
                                                int(bool(packed)), ptrs, len(comps), 1 if count else 0,
                                                self._ptr(psum, torch.float64), self._ptr(nsample, torch.int64)))
 
+    def fft_x_bin_helmholtz(self, comps, N, nlines, line0, kz0, nseg, seg_stride, psum, nsample, pcomp, count=True):
+        """fft_x_bin_multi of the three components of a vector field that also bins the compressive part of every mode,
+        |k'.F|^2 / |k'|^2, into pcomp (vps_fft_x_bin_helmholtz)."""
+        self._stream()
+        ptrs = (C.c_void_p * len(comps))(*[self._ptr(c, torch.complex64).value for c in comps])
+        self._chk(self.lib.vps_fft_x_bin_helmholtz(self.ctx, N, nlines, line0, kz0, ptrs, len(comps), nseg, seg_stride,
+                                                   1 if count else 0, self._ptr(psum, torch.float64),
+                                                   self._ptr(nsample, torch.int64), self._ptr(pcomp, torch.float64)))
+
+    def fft_x_bin_chunk_helmholtz(self, comps, N, nx, G, nchunks, chunk, rank, packed, psum, nsample, pcomp, count=True):
+        """fft_x_bin_chunk of the three components of a vector field with the compressive part binned into pcomp
+        (vps_fft_x_bin_chunk_helmholtz)."""
+        self._stream()
+        ptrs = (C.c_void_p * len(comps))(*[self._ptr(c, torch.complex64).value for c in comps])
+        self._chk(self.lib.vps_fft_x_bin_chunk_helmholtz(self.ctx, int(N), int(nx), int(G), int(nchunks), int(chunk), int(rank),
+                                                         int(bool(packed)), ptrs, len(comps), 1 if count else 0,
+                                                         self._ptr(psum, torch.float64), self._ptr(nsample, torch.int64),
+                                                         self._ptr(pcomp, torch.float64)))
+
     # -- the slab exchange inside the library (RCCL behind the C ABI) -------------
     @staticmethod
     def comm_unique_id():
@@ -968,7 +987,7 @@ class PowerPipeline:
         t0 = self._stamp()
         return {"handles": [self.comm.all_to_all_start(s_) for s_ in sends], "chunk": c, "packed": packed, "t0": t0}
 
-    def _finish_chunk(self, job, psum, nsample, count):
+    def _finish_chunk(self, job, psum, nsample, count, pcomp=None):
         N, nx, G, r = self.N, self.nx, self.comm.world, self.comm.rank
         t1 = self._stamp()
         recvs = [self.comm.all_to_all_finish(h) for h in job["handles"]]
@@ -976,6 +995,10 @@ class PowerPipeline:
         if t1 is not None:
             self.instr.append((job["t0"], t1, t2))      # exchange started | x pass ready to go | blocks there
         job["handles"] = None
+        if pcomp is not None:
+            self.k.fft_x_bin_chunk_helmholtz(recvs, N, nx, G, self.nchunks, job["chunk"], r, job["packed"], psum, nsample, pcomp,
+                                             count=count)
+            return
         self.k.fft_x_bin_chunk(recvs, N, nx, G, self.nchunks, job["chunk"], r, job["packed"], psum, nsample, count=count)
 
     def exchange_times(self):
@@ -992,19 +1015,29 @@ class PowerPipeline:
         deposit + z pass and returns its z images (one per component, which may live in the SAME buffer for every quantity:
         by then all y passes of quantity i - 1 have been enqueued); its chunks are binned into accumulators[i] =
         (psum, nsample).  counts[i] (default True): whether quantity i's shell counts are accumulated (first group only).
+        Helmholtz decomposition: accumulators[i] = (psum, nsample, pcomp) bins quantity i's three components in one launch
+        that also accumulates the compressive part into pcomp (VPS_X_PER_COMPONENT does not apply to it).
         What `bench.py` runs on several ranks (torch transport); one quantity: `accumulate_zimages`."""
         import collections
-        group = 1 if os.environ.get("VPS_X_PER_COMPONENT") == "1" else 3
+        if any(len(a) > 2 for a in accumulators):
+            self._check_helmholtz()
+        per_component = os.environ.get("VPS_X_PER_COMPONENT") == "1"
         k, C_, maxin = self.k, self.nchunks, self.inflight_max()
         inflight = collections.deque()
 
         def finish_oldest():
             job, qi, cnt = inflight.popleft()
-            self._finish_chunk(job, accumulators[qi][0], accumulators[qi][1], cnt)
+            acc = accumulators[qi]
+            self._finish_chunk(job, acc[0], acc[1], cnt, acc[2] if len(acc) > 2 else None)
         self.prepare()
         for qi, produce in enumerate(producers):
             zimgs = produce()
             cnt = True if counts is None else bool(counts[qi])
+            helm = len(accumulators[qi]) > 2
+            if helm and len(zimgs) != 3:
+                raise Exception("the Helmholtz decomposition needs the three components of a vector quantity (got %d z images)"
+                                % len(zimgs))
+            group = 1 if per_component and not helm else 3
             for i in range(0, len(zimgs), group):
                 for c in range(C_):
                     while len(inflight) >= maxin:
@@ -1038,6 +1071,22 @@ class PowerPipeline:
                 jobs[c] = None
         return psum, nsample
 
+    def _check_helmholtz(self):
+        """Refuse the Helmholtz decomposition where it is not implemented -- before anything is enqueued."""
+        if isinstance(self.comm, LibraryComm):
+            raise Exception("the Helmholtz decomposition is not available with LibraryComm (vps_spectrum_zimages bins |F|^2 "
+                            "only): use the torch.distributed transport (SlabComm)")
+
+    def accumulate_zimages_helmholtz(self, zimgs, acc=None, count=True):
+        """accumulate_zimages of the three z images of a vector quantity with the Helmholtz decomposition: -> (psum, nsample,
+        pcomp), pcomp the shell sums of the compressive part |k'.F|^2 / |k'|^2 (`new_accumulators(helmholtz=True)`)."""
+        self._check_helmholtz()
+        if len(zimgs) != 3:
+            raise Exception("the Helmholtz decomposition needs the three components of a vector quantity")
+        acc = self.new_accumulators(helmholtz=True) if acc is None else acc
+        self.pipelined_quantities([lambda: zimgs], [acc], counts=[count])
+        return acc
+
     def accumulate_zimages(self, zimgs, psum=None, nsample=None, count=True):
         """x-side of the transform for z images (HipKernels.fft_z / deposit_fft_z): per kz chunk, y pass into the
         send buffer, all-to-all, x pass + shell sums, two chunks in flight (`pipelined_quantities`)."""
@@ -1053,6 +1102,29 @@ class PowerPipeline:
         return psum, nsample
 
     # -- stage B + C on one or more real fields of this rank's slab ---------------
+    def accumulate_helmholtz(self, fields, acc=None, count=True, weight=None):
+        """`accumulate` of the three components of a vector quantity with the Helmholtz decomposition: -> (psum, nsample,
+        pcomp) -- psum, nsample exactly what `accumulate` adds, pcomp the shell sums of the compressive part
+        |k'.F|^2 / |k'|^2 of every mode (k' = integer mode numbers, Nyquist entries 0; `HipKernels.fft_x_bin_helmholtz`)."""
+        self._check_helmholtz()
+        if len(fields) != 3:
+            raise Exception("the Helmholtz decomposition needs the three components of a vector quantity")
+        N, nx = self.N, self.nx
+        k = self.k
+        k.set_binning(*self._binning)
+        self._set_window()
+        acc = self.new_accumulators(helmholtz=True) if acc is None else acc
+        if self.chunked:
+            zimgs = [k.fft_z(f, N, nx, weight=weight) for f in fields]
+            return self.accumulate_zimages_helmholtz(zimgs, acc, count)
+        pending = []
+        with self._bin_scope():
+            for f in fields:
+                spec, nyq = k.fft_zy(f, N, nx) if weight is None else k.fft_zy(f, N, nx, weight=weight)
+                pending.append((self.comm.all_to_all_start(spec), self.comm.all_to_all_start(nyq)))
+        self._bin_exchanged(pending, acc[0], acc[1], count, pcomp=acc[2])
+        return acc
+
     def accumulate(self, fields, psum=None, nsample=None, count=True, weight=None):
         """Add sum_w |F|^2 of every field ([nx,N,N] float32) into the shell sums, and (with
         `count`) the number of modes per shell into nsample -- once, on the first field: the
@@ -1078,14 +1150,20 @@ class PowerPipeline:
         self._bin_exchanged(pending, psum, nsample, count)
         return psum, nsample
 
-    def _bin_exchanged(self, pending, psum, nsample, count):
+    def _bin_exchanged(self, pending, psum, nsample, count, pcomp=None):
         """x pass + shell sums of exchanged spectra.  Up to three components at a time go through ONE
         launch that sums their |F|^2 before the shell search (what the reference does on the grid,
-        interp.py:1386, 1474-1477); VPS_X_PER_COMPONENT=1 bins every component on its own instead."""
+        interp.py:1386, 1474-1477); VPS_X_PER_COMPONENT=1 bins every component on its own instead.
+        pcomp (Helmholtz decomposition, three components): the compressive part is binned into it by the same launch."""
         N, nx, G, r = self.N, self.nx, self.comm.world, self.comm.rank
         k = self.k
         nkz, nky = N // 2 // G, N // G
         done = [(self.comm.all_to_all_finish(hs), self.comm.all_to_all_finish(hq)) for hs, hq in pending]
+        if pcomp is not None:
+            specs, nyqs = [d[0] for d in done], [d[1] for d in done]
+            k.fft_x_bin_helmholtz(specs, N, nkz * N, 0, r * nkz, G, nkz * N * nx, psum, nsample, pcomp, count=count)
+            k.fft_x_bin_helmholtz(nyqs, N, nky, r * nky, N // 2, G, nky * nx, psum, nsample, pcomp, count=count)
+            return
         group = 1 if os.environ.get("VPS_X_PER_COMPONENT") == "1" else 3
         for i in range(0, len(done), group):
             c = count and i == 0
@@ -1112,18 +1190,40 @@ class PowerPipeline:
         self._bin_exchanged(pending, psum, nsample, count)
         return psum, nsample
 
+    def accumulate_spectra_helmholtz(self, spec, nyq, acc=None, count=True):
+        """`accumulate_spectra` of the three z/y-transformed components (spec [3, N/2, N, nx], nyq [3, N, nx]) with the
+        Helmholtz decomposition: -> (psum, nsample, pcomp), as `accumulate_helmholtz`."""
+        self._check_helmholtz()
+        N, G = self.N, self.comm.world
+        if self.chunked:
+            raise Exception("several ranks exchange z images chunk by chunk: use HipKernels.deposit_fft_z / fft_z "
+                            "and PowerPipeline.accumulate_zimages_helmholtz")
+        if spec.shape[0] != 3 or nyq.shape[0] != 3:
+            raise Exception("the Helmholtz decomposition needs the three components of a vector quantity")
+        k = self.k
+        k.set_binning(*self._binning)
+        self._set_window()
+        acc = self.new_accumulators(helmholtz=True) if acc is None else acc
+        pending = [(self.comm.all_to_all_start(spec[i]), self.comm.all_to_all_start(nyq[i])) for i in range(3)]
+        self._bin_exchanged(pending, acc[0], acc[1], count, pcomp=acc[2])
+        return acc
+
     def _set_window(self):
         if hasattr(self.k, "set_window"):
             self.k.set_window(self.N, self.window)
         elif self.window is not None:
             raise Exception("this kernel set has no window deconvolution")
 
-    def new_accumulators(self):
+    def new_accumulators(self, helmholtz=False):
         """Zeroed shell sums (float64) and shell counts (int64) as two views of ONE device buffer, so that a
-        step clears them with one fill and `finish` brings them to the host with one copy."""
-        buf = self.k.zeros((2 * self.nbins,), torch.float64)
+        step clears them with one fill and `finish` brings them to the host with one copy.  helmholtz: a third view, the
+        float64 shell sums of the compressive part (`accumulate_helmholtz`), behind the other two."""
+        buf = self.k.zeros(((3 if helmholtz else 2) * self.nbins,), torch.float64)
         self._acc_buf = buf
-        return buf[: self.nbins], buf[self.nbins:].view(torch.int64)
+        nb = self.nbins
+        if helmholtz:
+            return buf[:nb], buf[nb: 2 * nb].view(torch.int64), buf[2 * nb:]
+        return buf[:nb], buf[nb:].view(torch.int64)
 
     def finish(self, psum, nsample, buf=None):
         """Reduce over ranks and build the reference's (nbins,4) table
@@ -1140,9 +1240,11 @@ class PowerPipeline:
         if (buf is not None and psum.data_ptr() == buf.data_ptr()
                 and nsample.data_ptr() == buf.data_ptr() + 8 * self.nbins):
             host = buf.cpu()                         # one device-to-host copy for both accumulators
+            self._acc_host = host if buf is getattr(self, "_acc_buf", None) else None
             ps = host[: self.nbins].numpy() * (0.5 * self.const ** 2)
-            ns = host[self.nbins:].view(torch.int64).numpy()
+            ns = host[self.nbins: 2 * self.nbins].view(torch.int64).numpy()
         else:
+            self._acc_host = None
             ps = psum.cpu().numpy() * (0.5 * self.const ** 2)
             ns = nsample.cpu().numpy()
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -1150,6 +1252,37 @@ class PowerPipeline:
         if self.flavour == "library":
             P[ns == 0] = 0                      # interp.py:1479
         return np.column_stack((self.centers, P, ps, ns.astype(np.float64)))
+
+    def finish_helmholtz(self, psum, nsample, pcomp):
+        """Reduce the three accumulators of `accumulate_helmholtz` over the ranks -> (total, compressive, solenoidal) tables
+        [centre, P, Psum, Nsample] before the 4 pi k^2 factor.  total is `finish`'s table; the solenoidal shell sums are the
+        float64 difference total - compressive; the three share the shell counts.  (Modes with k' = 0 -- k = 0 and the
+        axis-Nyquist modes such as (N/2, 0, 0) -- have no compressive part: they count as solenoidal.)"""
+        self._check_helmholtz()
+        self.comm.all_reduce_sum(pcomp)
+        tot = self.finish(psum, nsample)        # (one copy of all three when they are new_accumulators' views)
+        host = getattr(self, "_acc_host", None)
+        if host is not None and pcomp.data_ptr() == self._acc_buf.data_ptr() + 16 * self.nbins:
+            pc = host[2 * self.nbins: 3 * self.nbins].numpy() * (0.5 * self.const ** 2)
+        else:
+            pc = pcomp.cpu().numpy() * (0.5 * self.const ** 2)
+        ns = tot[:, 3]
+        out = [tot]
+        for ps in (pc, tot[:, 2] - pc):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                P = ps / ns
+            if self.flavour == "library":
+                P[ns == 0] = 0
+            out.append(np.column_stack((self.centers, P, ps, ns)))
+        return tuple(out)
+
+    def spectrum_helmholtz(self, fields, weight=None):
+        """(total, compressive, solenoidal) P(k) tables of the three components of a vector quantity (each multiplied cell
+        by cell by `weight` if given), times 4 pi k^2 (`accumulate_helmholtz`, `finish_helmholtz`)."""
+        tabs = self.finish_helmholtz(*self.accumulate_helmholtz(fields, weight=weight))
+        for tab in tabs:
+            tab[:, 1] *= 4 * np.pi * tab[:, 0] ** 2
+        return tabs
 
     def spectrum(self, fields, weight=None):
         """P(k) table of the fields (each multiplied cell by cell by `weight` if given), times 4 pi k^2."""

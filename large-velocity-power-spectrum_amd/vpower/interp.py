@@ -433,6 +433,51 @@ class BoxField:
         fields = self._fields(k, quantity)
         return PowerSpectrum(pipe.spectrum(fields))
 
+    def helmholtz_spctrm(self, quantity="velocity", kmin=None, kmax=None, kres=None, deconvolve=False):
+        """Helmholtz decomposition of the binned spectrum of a VECTOR quantity ('velocity' or 'momentum'; extension, the
+        reference has none): -> (total, compressive, solenoidal), three `PowerSpectrum`s of `spctrm`'s layout -- the same
+        shells, counts, edges, k range and window deconvolution, P multiplied by 4 pi k^2.  total is what `spctrm(quantity)`
+        returns; per mode, with F_c = fftn of component c and k'_i = fftfreq(N) * N on each axis with the Nyquist entry
+        (index N/2) set to 0,
+            P_comp = 0.5 |a|^2 |sum_c k'_c F_c|^2 / |k'|^2   (curl-free part; 0 where k' = 0)
+            P_sol  = P_tot - P_comp                          (divergence-free part; float64 difference of the shell sums)
+        so the modes with k' = 0 -- k = 0 and the axis-Nyquist modes such as (N/2, 0, 0), (N/2, N/2, 0) -- count as
+        solenoidal.  The projection is made in registers by the binning x pass (vps_fft_x_bin_helmholtz): no extra pass
+        over the spectrum.  Particle-backed fields go through the fused deposit as `spctrm` does (a second quantity of the
+        same field skips the particle sort; momentum leaves the energy field behind for `spctrm('energy')`)."""
+        if quantity not in ("velocity", "momentum"):
+            raise Exception("""Unrecognized physical quantity name.
+        Supported by the Helmholtz decomposition: 'velocity', 'momentum' (vector quantities).""")
+        k = _kernels()
+        pipe = _dev.PowerPipeline(self.Nsize, self.Lbox, kernels=k, comm=_dev.SlabComm(enabled=False),
+                                  flavour="library", kmin=kmin, kmax=kmax, kres=kres,
+                                  deconvolve=(getattr(self, "assignment", "ngp") if deconvolve else None))
+        flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
+        src = getattr(self, "_src", None)
+        nn = getattr(self, "_nn_src", None)
+        if src is not None and k.fused_supported(self.Nsize, _dev.QUANTITY[quantity]):
+            pipe.prepare()
+            with k.binning_only():      # the spectra go straight into the binning pass
+                spec, nyq = k.deposit_fft_zy(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize,
+                                             _dev.QUANTITY[quantity], flags, reuse_sort=getattr(self, "_sort_token", None),
+                                             share_energy=k.share_energy_fits(self.Nsize, self.Nsize))
+            self._sort_token = k.fused_token()
+            tabs = pipe.finish_helmholtz(*pipe.accumulate_spectra_helmholtz(spec, nyq))
+            for tab in tabs:
+                tab[:, 1] *= 4 * np.pi * tab[:, 0] ** 2
+        elif nn is not None and self._nn_spectra == 0:
+            self._nn_spectra = 1        # (as spctrm: the search writes this quantity's fields directly)
+            f, _ = k.nn_resample_quantity(nn[0], nn[1], (nn[2], nn[2], nn[2]), 0, self.Nsize, self.Lcell,
+                                          _dev.QUANTITY[quantity], flags)
+            tabs = pipe.spectrum_helmholtz([f[i] for i in range(3)])
+        elif quantity == "momentum":
+            ch = self._device_chans(k)
+            comps = [ch[0], ch[0], ch[0]] if REFERENCE_COMPAT["momentum_bug"] else [ch[0], ch[1], ch[2]]
+            tabs = pipe.spectrum_helmholtz(comps, weight=ch[3])
+        else:
+            tabs = pipe.spectrum_helmholtz(self._fields(k, quantity))
+        return tuple(PowerSpectrum(t) for t in tabs)
+
     # -- diagnostics (interp.py:639-666) ----------------------------------------------
     def _totals(self):
         """[sum m, sum m vx, sum m vy, sum m vz, sum m |v|^2]: one float64 device reduction over the
