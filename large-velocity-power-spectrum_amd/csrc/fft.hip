@@ -24,17 +24,6 @@
 
 #include "vps_internal.h"
 
-// Timing-only build switches (never defined by the product build; results are wrong or incomplete with them -- they exist so
-// that the ablations quoted in DESIGN.md can be repeated with tools/build_variant.sh + tools/time_pencil.py / time_xpass.py):
-//   VPS_PENCIL_NOSTORE  pencil kernel without its global stores      VPS_ABL_NOZERO / VPS_ABL_NOSCATTER  ... without the
-//   VPS_ABL_NOFFT       ... without transform, image and stores      accumulator's zero-fill / the LDS adds
-//   VPS_ABL_X_NOATOMIC / VPS_ABL_X_NOBIN   x pass without the LDS shell atomics / without the shell search and binning
-#ifndef VPS_Y_EARLY_G1
-#define VPS_Y_EARLY_G1 0   // wide y pass: the second group of lines requested ahead of the first group's transform (experiment)
-#endif
-#ifndef VPS_Y_ST16
-#define VPS_Y_ST16 1   // wide y pass: 16-byte stores (2048^3 launch 12.56 -> 12.10 ms; 0 restores the 8-byte epilogue)
-#endif
 namespace {
 
 typedef float2 cf;
@@ -537,14 +526,9 @@ __device__ __forceinline__ void exchange_sync() {
 // v_permlane16_swap (odd rows of vdst <-> even rows of vsrc) do a 4 x 4 row transpose of four registers in four instructions:
 // 32 VALU swaps replace 16 ds_write_b64 + 16 ds_read_b64 and a wave-level sync in a kernel whose LDS pipe is the busiest unit
 // (pencil kernel at C4: SQ_ACTIVE_INST_LDS x 16 waves ~ 90 % of the CU's cycles).  tools/micro/permlane_swap.hip pins the semantics.
-#ifndef VPS_NO_SWAP_EXCHANGE
-#define VPS_SWAP_EXCHANGE 1
-#else
-#define VPS_SWAP_EXCHANGE 0
-#endif
 template <int NC, int L, bool WAVE>
 constexpr bool swap_exchange2() {
-  return VPS_SWAP_EXCHANGE && WAVE && NC == 1024 && L == 64 && PlanInfo<NC>::R0 == 16 && PlanInfo<NC>::R1 == 8 && PlanInfo<NC>::R2 == 8;
+  return WAVE && NC == 1024 && L == 64 && PlanInfo<NC>::R0 == 16 && PlanInfo<NC>::R1 == 8 && PlanInfo<NC>::R2 == 8;
 }
 typedef unsigned vps_u2 __attribute__((ext_vector_type(2)));
 // y_b at lane row g = x_g at lane row b (rows of 16 lanes), in place
@@ -563,10 +547,9 @@ __device__ __forceinline__ void rows_transpose4(float& x0, float& x1, float& x2,
 // Runs stages 1.. (stage 0 inputs already in v).  On return v holds the spectrum:
 // v[m*RLAST + r] = F[l + L*m + r*NC/RLAST].  L lanes per line (default: the plan's; the persistent transposing pass
 // of the longest lines runs a line on half as many lanes with twice the points each).
-// TWREG: bit 0 -- the twiddles of stage 1 come from registers (twr1), bit 1 -- those of stage 2 (twr); see twiddle_butterfly_reg
-template <int NC, int L, bool WAVE, int TWREG = 0>
-__device__ __forceinline__ void fft_from_regs_l(cf (&v)[NC / L], cf* line, const cf* tw, int l, const cf* twr = nullptr,
-                                                const cf* twr1 = nullptr) {
+// TWREG: the twiddles of stage 2 come from registers (twr); see twiddle_butterfly_reg
+template <int NC, int L, bool WAVE, bool TWREG = false>
+__device__ __forceinline__ void fft_from_regs_l(cf (&v)[NC / L], cf* line, const cf* tw, int l, const cf* twr = nullptr) {
   typedef PlanInfo<NC> PI;
   constexpr int RL = NC / L;
   static_assert(RL % PI::R0 == 0 && RL % PI::R1 == 0 && RL % PI::R2 == 0, "radix must divide RL");
@@ -575,10 +558,7 @@ __device__ __forceinline__ void fft_from_regs_l(cf (&v)[NC / L], cf* line, const
     lds_store_stage<NC, L, RL, PI::R0, 1>(v, line, l);
     exchange_sync<WAVE>();
     lds_load_stage<NC, L, RL, PI::R1>(v, line, l);
-    if constexpr ((TWREG & 1) != 0)
-      twiddle_butterfly_reg<NC, L, RL, PI::R1, PI::NS1>(v, twr1);
-    else
-      twiddle_butterfly<NC, L, RL, PI::R1, PI::NS1>(v, tw, l);
+    twiddle_butterfly<NC, L, RL, PI::R1, PI::NS1>(v, tw, l);
     if constexpr (PI::R2 > 1) {
       if constexpr (swap_exchange2<NC, L, WAVE>()) {
 #pragma unroll
@@ -599,14 +579,14 @@ __device__ __forceinline__ void fft_from_regs_l(cf (&v)[NC / L], cf* line, const
         exchange_sync<WAVE>();
         lds_load_stage<NC, L, RL, PI::R2>(v, line, l);
       }
-      if constexpr ((TWREG & 2) != 0)
+      if constexpr (TWREG)
         twiddle_butterfly_reg<NC, L, RL, PI::R2, PI::NS2>(v, twr);
       else
         twiddle_butterfly<NC, L, RL, PI::R2, PI::NS2>(v, tw + PI::TW1, l);
     }
   }
 }
-template <int NC, bool WAVE = false, int TWREG = 0>
+template <int NC, bool WAVE = false, bool TWREG = false>
 __device__ __forceinline__ void fft_from_regs(cf (&v)[PlanInfo<NC>::RL], cf* line, const cf* tw, int l, const cf* twr = nullptr) {
   fft_from_regs_l<NC, PlanInfo<NC>::L, WAVE, TWREG>(v, line, tw, l, twr);
 }
@@ -692,13 +672,8 @@ __device__ __forceinline__ void r2c_store_tile(const cf* buf, int tid, const cf*
     const int idx = tid + i * NT;
     if ((PAIRS % NT) != 0 && idx >= PAIRS) break;
     const int tt = idx % T, k = idx / T;
-#ifdef VPS_PENCIL_NOSTORE
-    const cf zk = buf[tridx<T>(k, tt)];
-    const bool ok = (!BOUNDS || tt < nlive) && (zk.x == 1.2345e30f);   // TIMING ONLY: nothing is stored
-#else
     const bool ok = !BOUNDS || tt < nlive;
     const cf zk = buf[tridx<T>(k, tt)];
-#endif
     if (k == 0) {
       if (ok) {
         out[tt] = make_float2(zk.x + zk.y, 0.f);
@@ -730,12 +705,12 @@ __device__ __forceinline__ void r2c_store_tile(const cf* buf, int tid, const cf*
 
 // The same for 8-line tiles with 16-byte stores: a thread owns the lines (tt, tt + 1) of a mode pair, so a 64-byte output
 // segment leaves as four dwordx4 stores instead of eight dwordx2 (half the store instructions of the pencil kernel's epilogue).
-// zero_behind (uniform): every image element is cleared once it has been read (each is read by exactly one thread), so that the
-// region is an all-zero accumulator again when the epilogue ends -- the next component's dense zero-fill and the barrier behind
-// it move off the critical path into this store-issue-bound loop.
+// wpre: a thread's ITEMS / NT real-to-complex twiddles where a caller has loaded them ahead; none does (measured slower, DESIGN.md
+// section 7).  The parameter stays because without the select the compiler schedules the epilogue of the 8-line pencil kernels
+// differently, and the commit that retired that trial was held to byte-identical device code.
 template <int NC, int T, int NT, bool PLAIN = false>
-__device__ __forceinline__ void r2c_store_tile16(cf* buf, int tid, const cf* __restrict__ tw_r2c, cf* out,
-                                                 long long out_ok, cf* nyq, bool zero_behind = false, const cf* wpre = nullptr) {
+__device__ __forceinline__ void r2c_store_tile16(const cf* buf, int tid, const cf* __restrict__ tw_r2c, cf* out,
+                                                 long long out_ok, cf* nyq, const cf* wpre = nullptr) {
   static_assert((NC & 1) == 0 && (T & 1) == 0, "pairs of lines");
   constexpr int H = T / 2;
   constexpr int ITEMS = (NC / 2) * H;
@@ -744,28 +719,15 @@ __device__ __forceinline__ void r2c_store_tile16(cf* buf, int tid, const cf* __r
   for (int i = 0; i < ITEMS / NT; ++i) {
     const int idx = tid + i * NT;
     const int tt = (idx % H) * 2, k = idx / H;
-    const cf zz = make_float2(0.f, 0.f);
     const cf a0 = buf[tridx<T>(k, tt)], a1 = buf[tridx<T>(k, tt + 1)];
-    if (zero_behind) {
-      buf[tridx<T>(k, tt)] = zz;
-      buf[tridx<T>(k, tt + 1)] = zz;
-    }
     if (k == 0) {
       *reinterpret_cast<vps_f4*>(&out[tt]) = vps_f4{a0.x + a0.y, 0.f, a1.x + a1.y, 0.f};
       *reinterpret_cast<vps_f4*>(&nyq[tt]) = vps_f4{a0.x - a0.y, 0.f, a1.x - a1.y, 0.f};
       const cf h0 = buf[tridx<T>(NC / 2, tt)], h1 = buf[tridx<T>(NC / 2, tt + 1)];
-      if (zero_behind) {
-        buf[tridx<T>(NC / 2, tt)] = zz;
-        buf[tridx<T>(NC / 2, tt + 1)] = zz;
-      }
       *reinterpret_cast<vps_f4*>(&out[(long long)(NC / 2) * out_ok + tt]) = vps_f4{h0.x, -h0.y, h1.x, -h1.y};
     } else {
       const cf n0 = buf[tridx<T>(NC - k, tt)], n1 = buf[tridx<T>(NC - k, tt + 1)];
-      if (zero_behind) {
-        buf[tridx<T>(NC - k, tt)] = zz;
-        buf[tridx<T>(NC - k, tt + 1)] = zz;
-      }
-      const cf w = wpre ? wpre[i] : tw_r2c[k];   // (wpre: the thread's ITEMS / NT twiddles, loaded once per kernel)
+      const cf w = wpre ? wpre[i] : tw_r2c[k];
       const cf s0 = make_float2(a0.x + n0.x, a0.y - n0.y), d0 = make_float2(a0.x - n0.x, a0.y + n0.y);
       const cf s1 = make_float2(a1.x + n1.x, a1.y - n1.y), d1 = make_float2(a1.x - n1.x, a1.y + n1.y);
       const cf w0 = cmul(w, d0), w1 = cmul(w, d1);
@@ -976,17 +938,12 @@ __global__ void __launch_bounds__(TG* L, (NC == 1024 ? 4 : 1))
     const int a0 = (int)(tile % tiles) * T;
     const long long b = p.bg ? (long long)(bo / p.bg) * p.bg_in + p.b_off + (long long)(bo % p.bg) * p.bg_step : bo;   // batch as the input sees it
     const long long ogap = p.bg ? (long long)(bo / p.bg) * p.bg_gap : 0;
-#if VPS_Y_EARLY_G1
-    load_line(v1, tile, fresh(tid), TG);
-#endif
     {
       const int tida = fresh(tid);
       fft_from_regs_l<NC, L, WSYNC>(v0, buf + (tida / L) * PI::PITCH, tw, tida % L);
     }
     // (requesting the second group ahead of the first transform: 14.1 against 12.4 ms per 2048^3 launch)
-#if !VPS_Y_EARLY_G1
     load_line(v1, tile, fresh(tid), TG);
-#endif
     __syncthreads();  // every lane done with the per-line buffers
     {
       const int tidb = fresh(tid);
@@ -1013,7 +970,6 @@ __global__ void __launch_bounds__(TG* L, (NC == 1024 ? 4 : 1))
       if (h == 1 && ntiles - tile > gridDim.x) load_line(v0, tile + gridDim.x, fresh(tid), 0);
       __syncthreads();
       constexpr int IT = (NC / 2) * T / NT;
-#if VPS_Y_ST16
       // 16-byte stores: a lane owns the lines (tt, tt + 1) of a row, a 128-byte segment leaves as eight dwordx4 stores instead of
       // sixteen dwordx2 (the pencil kernel's epilogue gained 7 % from the same change: these epilogues are bound by store ISSUE)
       if (((p.out_ok | p.A) & 1) == 0 && (reinterpret_cast<size_t>(out) & 15) == 0) {   // (uniform)
@@ -1034,7 +990,6 @@ __global__ void __launch_bounds__(TG* L, (NC == 1024 ? 4 : 1))
         }
         continue;
       }
-#endif
 #pragma unroll 4
       for (int i = 0; i < IT; ++i) {
         const int idx = tid2 + i * NT;
@@ -1067,7 +1022,7 @@ struct PencilParams {
   const unsigned* records;   // (1 + 4) 32-bit words per particle, sorted by pencil
   const unsigned* start;     // [npencils + 1]
   int N, nx, nby;            // grid, slab rows, pencils per x row (N / TP)
-  unsigned npencils;         // pencils of the launch (the persistent form walks them: slot, slot + gridDim.x, ...)
+  unsigned npencils;         // pencils of the launch
   int ncomp;
   int chan[3];               // record channel (0..2) feeding component c
   int divide;                // 1: v = q / rho (0 where rho == 0);  0: p = q * vol
@@ -1083,81 +1038,11 @@ struct PencilParams {
   const cf* tw_r2c;
 };
 
-// tuning knobs (measured at 512^3 / 1024^3 / 2048^3): 4 waves/SIMD needs <= 128 VGPRs
-#ifndef VPS_PENCIL_MINW
-#define VPS_PENCIL_MINW 4
-#endif
-#ifndef VPS_PENCIL_MINW_LONG
-#define VPS_PENCIL_MINW_LONG 4
-#endif
-template <int NC>
-constexpr int pencil_min_waves() {
-  return NC >= 1024 ? VPS_PENCIL_MINW_LONG : VPS_PENCIL_MINW;
-}
-
-// Lanes per line: the plan's.  (While the kernel kept 1/rho -- and for energy the sums of squares -- per CELL in
-// registers, 2048-cell lines did not fit the 128 VGPRs of four waves per SIMD: it ran them on half the lanes, two waves
-// per SIMD, 83 ms per C4 step of which 65 ms were on-chip work that nothing overlapped.)
-#ifndef VPS_PENCIL_HALF_LANES_LONG
-#define VPS_PENCIL_HALF_LANES_LONG 0
-#endif
-template <int NC>
-constexpr int pencil_lanes() {
-  return (NC >= 1024 && VPS_PENCIL_HALF_LANES_LONG) ? PlanInfo<NC>::L / 2 : PlanInfo<NC>::L;
-}
-
-// Epilogue of 8-line pencils (2048- and 4096-cell lines; measured at C4, ms per launch, vector / energy): 8-byte streaming
-// stores 29.5 / 11.5 (rounds 2-3); 8-byte plain 30.6 / 10.95; 16-byte streaming 27.4 / 12.4; 16-byte plain 27.0 / 10.2 -- the
-// epilogue is bound by store ISSUE (half the instructions with dwordx4); the energy launch, whose workgroups live for one
-// component only, merges its half lines in L2 with the partner pencil's when they are not marked streaming (PMC: 44.9 -> 35.1 GB
-// written for 34.4 GB of output).
-#ifndef VPS_ST16_MODE
-#define VPS_ST16_MODE 3   // bit 0: vector launches, bit 1: the energy launch
-#endif
-#ifndef VPS_PLAIN_MODE
-#define VPS_PLAIN_MODE 2   // (vector launches with plain 16-byte stores: 27.0 ms on one box, 30.7 on two others, against 26.5 - 27.6 with
-#endif                     //  streaming stores everywhere; PMC 113.9 against 117.2 GB written for 103.2 GB of output: not worth the risk)
-#ifndef VPS_SHARED_E_PLAIN
-#define VPS_SHARED_E_PLAIN 1
-#endif
-#ifndef VPS_ST16_ALL
-#define VPS_ST16_ALL 0    // 1: 16-byte stores for 16-line pencils too (experiment)
-#endif
-// 1024-point lines on the plan's 64 lanes (the 2048^3 grid): the twiddles of both later stages depend on the lane alone and
-// CAN stay in registers for the whole kernel (7 + 7 values; the second butterfly of stage 2 by constant 16th-root rotations:
-// 28 of the 32 LDS reads per lane and transform that are not data) -- measured slower here, unlike in the x pass, see below.
-#ifndef VPS_PENCIL_R2C_PRELOAD
-#define VPS_PENCIL_R2C_PRELOAD 0
-#endif
-#ifndef VPS_PENCIL_ZERO_BEHIND
-#define VPS_PENCIL_ZERO_BEHIND 0   // the epilogue of a component clears the image behind itself: no dense zero-fill for the next one
-                                   // (measured at C4: vector launch 28.3 against 27.2 ms -- the epilogue is where the kernel is slowest)
-#endif
-#ifndef VPS_PENCIL_PERSIST
-#define VPS_PENCIL_PERSIST 0   // 1: persistent workgroups with the next pencil's records prefetched (see the kernel).  Measured at C4,
-                               // twice (rounds 2 and 4, the second time with the bounds, cells and first values of the next pencil
-                               // requested behind the last transform and the twiddles staged once): vector launch 27.3 against 26.5 ms,
-                               // energy 13.2 against 10.3 -- with or without holding every other workgroup back.  What the hardware
-                               // dispatcher gives for free -- workgroups of a CU out of step with each other -- is worth more than the
-                               // two dependent trips to HBM a fresh workgroup starts with.
-#endif
-#ifndef VPS_PENCIL_STAGGER
-#define VPS_PENCIL_STAGGER 0   // PERSIST: s_sleep(127) rounds by which the second workgroup of every CU starts late
-#endif
-#ifndef VPS_PENCIL_TWREG
-#define VPS_PENCIL_TWREG 0     // bit 0: stage 1, bit 1: stage 2.  Measured at C4 (vector / energy launch, ms): 0: 26.5 / 10.4;
-                               // 1: 27.8 / 11.8; 2: 27.2 / 12.1; 3 (7 registers spilled): 27.1 / 13.3 -- the LDS reads they save
-                               // cost less than the registers they take (80 -> 104..128 VGPRs): off
-#endif
-template <int NC>
-constexpr int pencil_twreg() {
-  typedef PlanInfo<NC> PI;
-  return (NC == 1024 && pencil_lanes<NC>() == 64 && PI::R1 == 8 && PI::R2 == 8) ? (VPS_PENCIL_TWREG) : 0;
-}
+// One workgroup per pencil, on the plan's lanes per line; four waves per SIMD (measured at 512^3 / 1024^3 / 2048^3) need <= 128 VGPRs.
 template <int NC, int TP, bool ENERGY = false>
-__global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()) pencil_fft_z_kernel(const PencilParams p) {
+__global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(const PencilParams p) {
   typedef PlanInfo<NC> PI;
-  constexpr int L = pencil_lanes<NC>(), RL = NC / L, NT = TP * L, N = 2 * NC;
+  constexpr int L = PI::L, RL = PI::RL, NT = TP * L, N = 2 * NC;
   constexpr int ACC = TP * N;                       // floats of one accumulator
   constexpr int LINES = TP * PI::PITCH * 2;         // floats of the exchange buffers
   constexpr int SHARED = (ACC > LINES ? ACC : LINES);
@@ -1167,13 +1052,7 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
   float* acc = reinterpret_cast<float*>(smem_raw);
   cf* buf = reinterpret_cast<cf*>(acc);
   cf* tw_lds = reinterpret_cast<cf*>(acc + SHARED);
-  constexpr int TWR = pencil_twreg<NC>();
-#ifdef VPS_PENCIL_TW_GLOBAL
-  constexpr bool TWL = false;
-#else
-  constexpr bool TWL = PI::TWLDS && TWR != 3;
-#endif
-  const cf* tw = TWL ? tw_lds : p.tw_stage;
+  const cf* tw = PI::TWLDS ? tw_lds : p.tw_stage;
 
   const int tid = threadIdx.x;
   const int t = tid / L, l = tid % L;
@@ -1181,39 +1060,17 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
   // pencil numbers; run them on ONE XCD, close in time, so that its L2 merges their partial-line writes (same map as
   // fft_transpose_pass: hardware block h = 8 s + x handles logical pencil G*(8*(s/G) + x) + s%G)
   constexpr unsigned GP = (TP < 16) ? 16 / TP : 1;
-  auto map_slot = [&](unsigned slot) -> unsigned {
-    if constexpr (GP > 1) {
-      const unsigned span = 8 * GP;
-      if (slot / span < p.npencils / span) {   // whole groups only; the tail keeps the identity map
-        const unsigned base = (slot / span) * span, h = slot % span;
-        return base + GP * (h % 8) + (h / 8);
-      }
+  unsigned pencil = blockIdx.x;
+  if constexpr (GP > 1) {
+    constexpr unsigned span = 8 * GP;
+    if (pencil / span < p.npencils / span) {   // whole groups only; the tail keeps the identity map
+      const unsigned h = pencil % span;
+      pencil = (pencil / span) * span + GP * (h % 8) + (h / 8);
     }
-    return slot;
-  };
-  // PERSIST (VPS_PENCIL_PERSIST): the workgroup walks pencil slots blockIdx.x, + gridDim.x, ... -- the twiddles are staged
-  // once, and the bucket bounds, cells and first values of the NEXT pencil are requested behind the last component's
-  // transform, so that a pencil no longer begins with two dependent trips to HBM (bounds, then records) and a table copy.
-  constexpr bool PERSIST = VPS_PENCIL_PERSIST != 0;
-  unsigned slot = blockIdx.x;
-  unsigned pencil = map_slot(slot);
-  unsigned s = p.start[pencil], e = p.start[pencil + 1];
-  unsigned s_n = 0, e_n = 0, pencil_n = 0;
-  if constexpr (TWL)
-    for (int i = tid; i < PI::TW; i += NT) tw_lds[i] = p.tw_stage[i];
-  // the real-to-complex twiddles of this thread's rows in the 16-byte epilogue: k = tid / (TP / 2) + i NT / (TP / 2), the same
-  // for every component (and pencil) -- loaded once instead of one dependent global load per component ahead of the stores
-  constexpr int WHO0 = ENERGY ? 2 : 1;
-  constexpr bool ST16_0 = (VPS_ST16_MODE & WHO0) && TP >= 8 && TP <= 16 && (VPS_ST16_ALL || TP == 8) && (NC & 1) == 0 && ((NC / 2) * (TP / 2)) % NT == 0;
-  constexpr int NW = (ST16_0 && VPS_PENCIL_R2C_PRELOAD) ? ((NC / 2) * (TP / 2)) / NT : 0;
-  cf wr2c[NW > 0 ? NW : 1];
-  if constexpr (NW > 0) {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) wr2c[i] = p.tw_r2c[(tid + i * NT) / (TP / 2)];
   }
-  cf twr1[(TWR & 1) ? (PI::R1 - 1) : 1], twr2[(TWR & 2) ? (PI::R2 - 1) : 1];
-  if constexpr ((TWR & 1) != 0) load_stage_twiddles<NC, L, RL, PI::R1, PI::NS1>(twr1, p.tw_stage, l);
-  if constexpr ((TWR & 2) != 0) load_stage_twiddles<NC, L, RL, PI::R2, PI::NS2>(twr2, p.tw_stage + PI::TW1, l);
+  const unsigned s = p.start[pencil], e = p.start[pencil + 1];
+  if constexpr (PI::TWLDS)
+    for (int i = tid; i < PI::TW; i += NT) tw_lds[i] = p.tw_stage[i];
   // What a CELL needs besides the sums -- 1/rho (velocity), the running sum of (rho v_c)^2 (energy) -- is kept per RECORD:
   // every record of a cell reads the cell's total from the accumulator and carries the same value.  A per-cell table would
   // be RL register pairs per lane next to the RL transform registers (it was: the kernel then fit four waves per SIMD only
@@ -1223,16 +1080,10 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
   // inside a round (tail loops below); their per-record value lives in p.side[record].
   // register-resident record groups: enough for a typical bucket (~1.2 x mean occupancy at the bench
   // densities) -- 3 x 256 threads at 512^3, 2 x 512 at 1024^3 (measured optimum each)
-#ifdef VPS_PENCIL_KR
-  constexpr int KR = VPS_PENCIL_KR;
-#else
   constexpr int KR = NT >= 512 ? 2 : (NT >= 256 ? 3 : 4);
-#endif
   unsigned rloc[KR];
   float rval[KR];
   float rrec[KR];   // 1/rho of the record's cell (velocity) / sum over components of (rho v_c)^2 of its cell (ENERGY)
-  unsigned rloc_n[PERSIST ? KR : 1];
-  float rval_n[PERSIST ? KR : 1];
   auto fetch = [&](int word) {   // record word 1..3: rho v_c, 4: rho
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
@@ -1249,28 +1100,9 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
   fetch(divide ? 4 : 1 + p.chan[0]);
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   constexpr int R0 = PI::R0, NB0 = RL / R0;
-#if VPS_PENCIL_STAGGER
-  // the two workgroups of a CU start together and would stay in step (both accumulating, both storing): hold every other one back
-  if (PERSIST && (blockIdx.x / (gridDim.x / 2)) != 0)
-    for (int i = 0; i < VPS_PENCIL_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
- for (;;) {   // (one pass per pencil; a single pass unless PERSIST)
-  if constexpr (PERSIST) {
-    __syncthreads();   // the previous pencil's transposed image is consumed
-    const unsigned nxt = slot + gridDim.x;
-    if (nxt < p.npencils) {     // bounds of the next pencil: needed at the END of this pass
-      pencil_n = map_slot(nxt);
-      s_n = p.start[pencil_n];
-      e_n = p.start[pencil_n + 1];
-    }
-  }
   const int x = pencil / p.nby, y0 = (pencil % p.nby) * TP;
   // more than two particles per cell on average: hot cells are likely, take the native atomics (vps_lds_add)
-#ifdef VPS_PENCIL_NATIVE_ADD
-  const bool crowded = true;
-#else
   const bool crowded = (e - s) > 2u * (unsigned)ACC;
-#endif
 #pragma unroll
   for (int k = 0; k < KR; ++k) rrec[k] = 1.f;
   const unsigned tail0 = s + tid + KR * NT;   // this thread's first record beyond the register-resident ones
@@ -1307,9 +1139,7 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
     // opaque copies: keeps the compiler from hoisting ~50 loop-invariant LDS addresses out of the
     // component loop (they cost more registers than they save instructions, and an occupancy step)
     int lc = l, tc = t, tidc = tid;
-#ifndef VPS_PENCIL_NO_OPAQUE
     asm volatile("" : "+v"(lc), "+v"(tc), "+v"(tidc));
-#endif
     lc &= L - 1;   // give the value ranges back to the compiler (address folding needs them)
     tc &= TP - 1;
     tidc &= NT - 1;
@@ -1319,32 +1149,22 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
     // 4-byte writes) instead of a dense fill of the whole region (64 - 128 KB at the LDS write rate: 830 - 1500 clk per round).
     // After a transform the region is FFT scratch and needs the dense fill.
     const bool sparse_clear = ENERGY ? (c > 0) : (divide && c == 0);
-    // ZB: the previous component's epilogue left the region all zero behind itself (r2c_store_tile16: zero_behind)
-    constexpr int WHO_ = ENERGY ? 2 : 1;
-    constexpr bool ZB = VPS_PENCIL_ZERO_BEHIND && !ENERGY && (VPS_ST16_MODE & WHO_) && TP == 8 && (NC & 1) == 0 &&
-                        ((NC / 2) * (TP / 2)) % NT == 0 && ACC * 4 <= NC * TP * 8;
-    const bool prezeroed = ZB && c > 0;
-    if (prezeroed) {
-    } else if (sparse_clear) {
+    if (sparse_clear) {
 #pragma unroll
       for (int k = 0; k < KR; ++k)
         if (rloc[k] != 0xffffffffu) acc[rloc[k]] = 0.f;
       for (unsigned j = tail0; j < e; j += NT) acc[p.records[(size_t)j * 5]] = 0.f;
     } else {
-#ifndef VPS_ABL_NOZERO
       for (int i = tid; i < ACC / 4; i += NT) reinterpret_cast<float4*>(acc)[i] = zero4;
-#endif
     }
-    if (!prezeroed) __syncthreads();
+    __syncthreads();
     const bool rho_round = (ENERGY || we) && c == p.ncomp;
     const int word = rho_round ? 4 : 1 + p.chan[c < p.ncomp ? c : 0];
     // velocity: each term is divided by its cell's rho as it is added -- sum_k (q_k / rho) for the reference's
     // (sum_k q_k) / rho: a different rounding of the same value, within the float32 accumulation noise of the sums
-#ifndef VPS_ABL_NOSCATTER
 #pragma unroll
     for (int k = 0; k < KR; ++k)
       if (rloc[k] != 0xffffffffu) vps_lds_add(&acc[rloc[k]], divide ? rval[k] * rrec[k] : rval[k], crowded);
-#endif
     if (c + 1 < nround) fetch(((ENERGY || we) && c + 1 == p.ncomp) ? 4 : 1 + p.chan[c + 1 < p.ncomp ? c + 1 : 0]);
     for (unsigned j = tail0; j < e; j += NT) {
       const unsigned* rec = p.records + (size_t)j * 5;
@@ -1404,25 +1224,7 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
     }
     __syncthreads();   // accumulator of this component consumed: its memory becomes FFT scratch
     constexpr bool WSYNC = (L <= 64) && (64 % L == 0);
-#ifdef VPS_ABL_NOFFT
-#pragma unroll
-    for (int i = 0; i < RL; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y));
-    if (v[0].x != 1.2345e30f) continue;
-#endif
-    if constexpr (PERSIST) {
-      // last round: the records of this pencil are done with -- request the next pencil's cells and first values now, they
-      // land behind this transform and its stores
-      if (c + 1 == nround && slot + gridDim.x < p.npencils) {
-        const int w0 = divide ? 4 : 1 + p.chan[0];
-#pragma unroll
-        for (int k = 0; k < KR; ++k) {
-          const unsigned j = s_n + tid + k * NT;
-          rloc_n[k] = (j < e_n) ? p.records[(size_t)j * 5] : 0xffffffffu;
-          if (j < e_n) rval_n[k] = __uint_as_float(p.records[(size_t)j * 5 + w0]);
-        }
-      }
-    }
-    fft_from_regs_l<NC, L, WSYNC, TWR>(v, buf + tc * PI::PITCH, tw, lc, twr2, twr1);
+    fft_from_regs_l<NC, L, WSYNC>(v, buf + tc * PI::PITCH, tw, lc);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < RL; ++i) buf[tridx<TP>(out_index_l<NC, L>(lc, i), tc)] = v[i];
@@ -1430,37 +1232,23 @@ __global__ void __launch_bounds__(TP* pencil_lanes<NC>(), pencil_min_waves<NC>()
     const int oc = ENERGY ? 0 : c;
     cf* out = p.out[oc] + (long long)x * NC * N + y0;
     cf* nyq = p.nyq[oc] + (long long)x * N + y0;
-    // epilogue flavour of 8-line pencils (64-byte output segments): 16-byte stores and / or plain instead of streaming stores,
-    // per kernel (bit 0: vector launches, bit 1: the energy launch) -- measured at C4, DESIGN.md section 7
-    constexpr int WHO = ENERGY ? 2 : 1;
-    constexpr bool ST16 = (VPS_ST16_MODE & WHO) && TP >= 8 && TP <= 16 && (VPS_ST16_ALL || TP == 8) && (NC & 1) == 0 && ((NC / 2) * (TP / 2)) % NT == 0;
-    constexpr bool PLAIN = (VPS_PLAIN_MODE & WHO) && TP < 16;
+    // 8-line pencils (64-byte output segments) leave in 16-byte stores: the epilogue is bound by store ISSUE (half the
+    // instructions with dwordx4).  Plain stores for the energy launch and for the energy field of a with_energy launch -- a
+    // workgroup's LAST field: its half lines merge in L2 with the partner pencil's when they are not marked streaming (PMC: 44.9 ->
+    // 35.1 GB written for 34.4 GB of output); streaming stores otherwise.  Measured at C4: DESIGN.md section 7.
+    constexpr bool ST16 = TP == 8 && (NC & 1) == 0 && ((NC / 2) * (TP / 2)) % NT == 0;
     if constexpr (ST16) {
-      // (the energy field of a with_energy launch is the workgroup's LAST component, like the one field of an energy launch:
-      //  plain stores there too, so that the half lines of partner pencils meet in L2 -- VPS_SHARED_E_PLAIN)
-      if (VPS_SHARED_E_PLAIN && !ENERGY && !PLAIN && rho_round)
-        r2c_store_tile16<NC, TP, NT, true>(buf, tidc, p.tw_r2c, out, N, nyq, false, nullptr);
+      if (ENERGY || rho_round)
+        r2c_store_tile16<NC, TP, NT, true>(buf, tidc, p.tw_r2c, out, N, nyq);
       else
-        r2c_store_tile16<NC, TP, NT, PLAIN>(buf, tidc, p.tw_r2c, out, N, nyq, ZB && c + 1 < nround, NW > 0 ? wr2c : nullptr);
+        r2c_store_tile16<NC, TP, NT, false>(buf, tidc, p.tw_r2c, out, N, nyq);
     } else
-      r2c_store_tile<NC, TP, NT, false, PLAIN>(buf, tidc, p.tw_r2c, out, N, nyq, TP);
+      r2c_store_tile<NC, TP, NT, false, ENERGY && TP < 16>(buf, tidc, p.tw_r2c, out, N, nyq, TP);
   }
-  if constexpr (!PERSIST) break;
-  slot += gridDim.x;
-  if (slot >= p.npencils) break;
-  pencil = pencil_n;
-  s = s_n;
-  e = e_n;
-#pragma unroll
-  for (int k = 0; k < KR; ++k) {
-    rloc[k] = rloc_n[PERSIST ? k : 0];
-    rval[k] = rval_n[PERSIST ? k : 0];
-  }
- }
 }
 
 // ------------------------------------------------------------------------------
-// Epilogue of the kernels that transform a pencil of TP lines in two halves of TP/2 lines (split pencil, pencil pair): thread
+// Epilogue of the kernel that transforms a pencil of TP lines in two halves of TP/2 lines (split pencil): thread
 // (t, l) holds the spectrum of line t in `vpark` and of line t + TP/2 in `v`.  The transposed image of all TP lines does not
 // fit next to nothing else: it is staged in two halves of the mode PAIRS -- the real-to-complex step needs Z[k] with Z[NC - k]:
 // after the last radix-R stage register slot (m, r) holds k = l + L m + r NC/R, so r < R/4 and r >= 3R/4 are exactly the modes
@@ -1553,9 +1341,9 @@ __device__ __forceinline__ void two_half_image_store(cf* buf, cf* edge, const cf
 // 1/rho and energy sums, sparse clears, CAS-first LDS adds, the 16-byte epilogue -- is the pencil kernel's.
 // ------------------------------------------------------------------------------
 template <int NC, int TP, bool ENERGY>
-__global__ void __launch_bounds__((TP / 2) * pencil_lanes<NC>(), 4) pencil_split_fft_z_kernel(const PencilParams p) {
+__global__ void __launch_bounds__((TP / 2) * PlanInfo<NC>::L, 4) pencil_split_fft_z_kernel(const PencilParams p) {
   typedef PlanInfo<NC> PI;
-  constexpr int L = pencil_lanes<NC>(), RL = NC / L, TH = TP / 2, NT = TH * L, N = 2 * NC;
+  constexpr int L = PI::L, RL = PI::RL, TH = TP / 2, NT = TH * L, N = 2 * NC;
   constexpr int R = LastRadix<NC>::R;
   static_assert(TP == 8 && (R % 4) == 0 && (NC % 4) == 0, "eight lines in two halves, image in two halves of the mode pairs");
   constexpr int ACC = TH * N;                       // floats of one accumulator (four lines)
@@ -1775,202 +1563,19 @@ __global__ void __launch_bounds__((TP / 2) * pencil_lanes<NC>(), 4) pencil_split
   }
 }
 
-// ------------------------------------------------------------------------------
-// Pencil PAIR: two neighbouring 8-line pencils (y0 .. y0 + 7 and y0 + 8 .. y0 + 15 -- consecutive buckets of the sort) in ONE
-// workgroup of the 8-line kernel's shape.  The halves run one after the other through the 8-line kernel's rounds and
-// transform (same LDS region, same threads; each half scans only its own bucket); the first half's spectrum waits in registers,
-// and the epilogue stores the 16 lines together: whole 128-byte lines with 16-byte stores, where two separate pencils wrote 64-byte
-// halves that only sometimes met in L2 (PMC: 117 GB written for 103 GB of output in a vector launch at 2048^3).
-// ------------------------------------------------------------------------------
-template <int NC, bool ENERGY>
-__global__ void __launch_bounds__(8 * pencil_lanes<NC>(), 4) pencil_pair_fft_z_kernel(const PencilParams p) {
-  typedef PlanInfo<NC> PI;
-  constexpr int TH = 8, TP = 16;
-  constexpr int L = pencil_lanes<NC>(), RL = NC / L, NT = TH * L, N = 2 * NC;
-  constexpr int ACC = TH * N;                       // floats of one accumulator (eight lines)
-  constexpr int LINES = TH * PI::PITCH * 2;         // floats of the exchange buffers
-  constexpr int IMG = (NC / 2) * TP * 2;            // floats of half an image: NC/2 modes x 16 lines
-  constexpr int SHARED = (ACC > LINES ? (ACC > IMG ? ACC : IMG) : (LINES > IMG ? LINES : IMG));
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* acc = reinterpret_cast<float*>(smem_raw);
-  cf* buf = reinterpret_cast<cf*>(acc);
-  cf* edge = reinterpret_cast<cf*>(acc + SHARED);
-  cf* tw_lds = edge + TP;
-  constexpr bool TWL = PI::TWLDS;
-  const cf* tw = TWL ? tw_lds : p.tw_stage;
-
-  const int tid = threadIdx.x;
-  const int t = tid / L, l = tid % L;
-  const unsigned nby2 = (unsigned)p.nby / 2u;
-  const unsigned pair = blockIdx.x;
-  const int x = pair / nby2, y0 = (pair % nby2) * TP;
-  const unsigned p0 = (unsigned)x * (unsigned)p.nby + 2u * (pair % nby2);
-  const unsigned sA = p.start[p0], sB = p.start[p0 + 1], eB = p.start[p0 + 2];
-  if constexpr (TWL)
-    for (int i = tid; i < PI::TW; i += NT) tw_lds[i] = p.tw_stage[i];
-  // per half one register-resident record per thread (a bucket of 8 lines holds ~190 records at the bench density, 512
-  // threads); fuller buckets read the rest inside the rounds (tail loops; their per-record value lives in p.side[record])
-  unsigned rloc[2];
-  float rval[2], rrec[2];
-  const unsigned hs[2] = {sA, sB}, he[2] = {sB, eB};
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const unsigned j = hs[h] + tid;
-    rloc[h] = (j < he[h]) ? p.records[(size_t)j * 5] : 0xffffffffu;
-    rrec[h] = 1.f;
-  }
-  const bool divide = !ENERGY && p.divide;
-  auto fetch = [&](int h, int word) {   // record word 1..3: rho v_c, 4: rho
-    const unsigned j = hs[h] + tid;
-    if (j < he[h]) rval[h] = __uint_as_float(p.records[(size_t)j * 5 + word]);
-  };
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  constexpr int R0 = PI::R0, NB0 = RL / R0;
-  constexpr bool WSYNC = (L <= 64) && (64 % L == 0);
-  auto dense_clear = [&]() {
-    for (int i = tid; i < ACC / 4; i += NT) reinterpret_cast<float4*>(acc)[i] = zero4;
-  };
-  auto sparse_clear = [&](int h) {
-    if (rloc[h] != 0xffffffffu) acc[rloc[h]] = 0.f;
-    for (unsigned j = hs[h] + tid + NT; j < he[h]; j += NT) acc[p.records[(size_t)j * 5]] = 0.f;
-  };
-  // one accumulation round of half h: the value in rval[h] (word `word` of the tail records), times 1/rho when dividing
-  auto scatter = [&](int h, int word, bool times_rrec, bool crowded) {
-    if (rloc[h] != 0xffffffffu) vps_lds_add(&acc[rloc[h]], times_rrec ? rval[h] * rrec[h] : rval[h], crowded);
-    for (unsigned j = hs[h] + tid + NT; j < he[h]; j += NT) {
-      const unsigned* rec = p.records + (size_t)j * 5;
-      const float val = __uint_as_float(rec[word]);
-      vps_lds_add(&acc[rec[0]], times_rrec ? val * p.side[j] : val, crowded);
-    }
-  };
-  const bool crowdedh[2] = {(sB - sA) > 2u * (unsigned)ACC, (eB - sB) > 2u * (unsigned)ACC};
-
-  // ---- velocity: 1 / rho of every record's cell; the second half first, so that the accumulator holds the FIRST half's rho
-  // when its first component starts (sparse clear there) ----
-  if (divide) {
-    fetch(1, 4);
-    fetch(0, 4);
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {   // (unrolled: h indexes register arrays)
-      const int h = 1 - hh;
-      __syncthreads();
-      dense_clear();
-      __syncthreads();
-      scatter(h, 4, false, crowdedh[h]);
-      __syncthreads();
-      if (rloc[h] != 0xffffffffu) {
-        const float r = acc[rloc[h]];
-        rrec[h] = r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
-      }
-      for (unsigned j = hs[h] + tid + NT; j < he[h]; j += NT) {
-        const float r = acc[p.records[(size_t)j * 5]];
-        p.side[j] = r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
-      }
-    }
-  }
-
-  const int nfields = ENERGY ? 1 : p.ncomp;
-  for (int c = 0; c < nfields; ++c) {
-    cf vpark[RL], v[RL];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // (unrolled: h indexes register arrays)
-      int lc = l, tc = t;
-      asm volatile("" : "+v"(lc), "+v"(tc));   // (keeps the LDS addresses of the two halves from being formed up front)
-      lc &= L - 1;
-      tc &= TH - 1;
-      if constexpr (ENERGY) {
-        // the three rho v_c rounds add up q_c^2 per record, a fourth accumulates rho and finishes E = vol * sum / rho
-        fetch(h, 1 + p.chan[0]);
-        for (int cc = 0; cc < p.ncomp; ++cc) {
-          __syncthreads();
-          if (cc == 0) dense_clear(); else sparse_clear(h);
-          __syncthreads();
-          scatter(h, 1 + p.chan[cc], false, crowdedh[h]);
-          fetch(h, cc + 1 < p.ncomp ? 1 + p.chan[cc + 1] : 4);
-          __syncthreads();
-          if (rloc[h] != 0xffffffffu) {
-            const float q = acc[rloc[h]];
-            rrec[h] = (cc == 0) ? q * q : rrec[h] + q * q;
-          }
-          for (unsigned j = hs[h] + tid + NT; j < he[h]; j += NT) {
-            const float q = acc[p.records[(size_t)j * 5]];
-            p.side[j] = (cc == 0) ? q * q : p.side[j] + q * q;
-          }
-        }
-        __syncthreads();
-        sparse_clear(h);
-        __syncthreads();
-        scatter(h, 4, false, crowdedh[h]);
-        __syncthreads();
-        if (rloc[h] != 0xffffffffu) {
-          const float r = acc[rloc[h]];
-          rrec[h] = r != 0.f ? rrec[h] * __builtin_amdgcn_rcpf(r) * p.vol : 0.f;
-        }
-        for (unsigned j = hs[h] + tid + NT; j < he[h]; j += NT) {
-          const float r = acc[p.records[(size_t)j * 5]];
-          p.side[j] = r != 0.f ? p.side[j] * __builtin_amdgcn_rcpf(r) * p.vol : 0.f;
-        }
-        __syncthreads();
-        if (rloc[h] != 0xffffffffu) acc[rloc[h]] = rrec[h];
-        for (unsigned j = hs[h] + tid + NT; j < he[h]; j += NT) acc[p.records[(size_t)j * 5]] = p.side[j];
-      } else {
-        if (c == 0 && !divide) fetch(h, 1 + p.chan[0]);
-        if (c == 0 && divide && h == 0) {
-          fetch(0, 1 + p.chan[0]);
-          fetch(1, 1 + p.chan[0]);
-        }
-        __syncthreads();   // previous image / the other half's exchange buffers consumed
-        if (divide && c == 0 && h == 0) sparse_clear(0); else dense_clear();
-        __syncthreads();
-        scatter(h, 1 + p.chan[c], divide, crowdedh[h]);
-        if (c + 1 < nfields) fetch(h, 1 + p.chan[c + 1]);
-      }
-      __syncthreads();
-      {
-        const float* q = acc + tc * N;
-        const float sc = (ENERGY || divide) ? 1.f : p.vol;
-#pragma unroll
-        for (int m = 0; m < NB0; ++m)
-#pragma unroll
-          for (int rr = 0; rr < R0; ++rr) {
-            const int j = lc + L * m + rr * (NC / R0);
-            const float2 qq = *reinterpret_cast<const float2*>(q + 2 * j);
-            v[m * R0 + rr] = make_float2(qq.x * sc, qq.y * sc);
-          }
-      }
-      __syncthreads();   // accumulator consumed: its memory becomes FFT scratch
-      fft_from_regs_l<NC, L, WSYNC>(v, buf + tc * PI::PITCH, tw, lc);
-      if (h == 0) {
-#pragma unroll
-        for (int i = 0; i < RL; ++i) vpark[i] = v[i];
-      }
-    }
-    cf* out = p.out[c] + (long long)x * NC * N + y0;
-    cf* nyq = p.nyq[c] + (long long)x * N + y0;
-    two_half_image_store<NC, TP, L, !ENERGY>(buf, edge, vpark, v, l, t, tid, out, nyq, p.tw_r2c);
-  }
-}
-
 // (A wave-private form -- every wave scans all records of the pencil, keeps those of its own line(s) and runs zero-fill, LDS
 // adds, read-back, stage-0 loads and the exchanges inside its own LDS region with wave-level ordering only, three workgroup
 // barriers per component instead of seven -- measured at C4: 97 against 75 ms per step of pencil launches, bit-identical
 // results.  The barriers are not what the kernel waits for; eight-fold record scans and 64-lane zero-fills cost more.)
-// (A persistent form of the pencil kernel -- workgroups walking pencil slots, the next pencil's bucket bounds, cells and
-// first values requested behind the last component's stores -- measured slower: 32.5 against 30.6 ms per C4 vector launch,
-// 16.1 against 13.0 for energy, 0.48 against 0.39 ms at C2.  Unlike the y pass's tiles, pencils differ in work; the
-// hardware dispatcher balances them, a fixed stride does not.)
-// y-lines per pencil: 16 (128-byte output segments); 8 for 2048-cell lines, on half the plan's lanes (pencil_lanes): 256
+// y-lines per pencil: 16 (128-byte output segments); 8 from 2048-cell lines on: at 2048 cells 512
 // threads and 76 KB of LDS per workgroup, so TWO workgroups share a CU and one's stores overlap the other's LDS work.  The two
 // pencils that complete a 128-byte output line are placed on one XCD (remap in the kernel); 38 % of the lines still
 // reach HBM as two halves (PMC WRITE_SIZE 142 GB for 103 GB of output), which costs less than the lost overlap.
 // Measured at C4 (2048^3, ms per step of 7 fields): 16 lines x 64 lanes, spilling 111; 8 x 64 spilling 118, not spilling
 // (two waves per SIMD) 106; 16 x 32 (one workgroup per CU, full-line writes) 88; 8 x 32 83; 4 x 64 (32-byte segments) 228.
-#ifndef VPS_PENCIL_TP_LONG
-#define VPS_PENCIL_TP_LONG 8
-#endif
 template <int NC>
-constexpr int pencil_tp() {
-  return NC >= 1024 ? VPS_PENCIL_TP_LONG : 16;
+constexpr int pencil_tp() {   // (vps_pencil_tp() is the same rule for the host's callers)
+  return NC >= 1024 ? 8 : 16;
 }
 
 template <int NC>
@@ -1978,19 +1583,9 @@ size_t pencil_lds_bytes() {
   typedef PlanInfo<NC> PI;
   constexpr int PENCIL_TP = pencil_tp<NC>();
   constexpr int ACC = PENCIL_TP * 2 * NC, LINES = PENCIL_TP * PI::PITCH * 2;
-  return (size_t)(ACC > LINES ? ACC : LINES) * sizeof(float) + (size_t)(pencil_twreg<NC>() == 3 ? 0 : PI::TWL) * sizeof(cf);
+  return (size_t)(ACC > LINES ? ACC : LINES) * sizeof(float) + (size_t)PI::TWL * sizeof(cf);
 }
 
-// which line lengths run the split form (pencil_split_fft_z_kernel): bit 0 -- 1024 packed points (2048-cell lines), bit 1 -- 2048
-// (4096-cell lines, where the whole pencil leaves one workgroup per CU)
-#ifndef VPS_PENCIL_SPLIT
-#define VPS_PENCIL_SPLIT 2
-#endif
-template <int NC>
-constexpr bool pencil_split() {
-  return pencil_tp<NC>() == 8 && (LastRadix<NC>::R % 4) == 0 &&
-         ((NC == 1024 && (VPS_PENCIL_SPLIT & 1)) || (NC == 2048 && (VPS_PENCIL_SPLIT & 2)));
-}
 template <int NC>
 size_t pencil_split_lds_bytes() {
   typedef PlanInfo<NC> PI;
@@ -2000,41 +1595,12 @@ size_t pencil_split_lds_bytes() {
   return shared * sizeof(float) + (size_t)pencil_tp<NC>() * sizeof(cf);
 }
 
-// which launches of 2048-cell lines run as pencil pairs (pencil_pair_fft_z_kernel): bit 0 -- vector launches, bit 1 -- energy
-#ifndef VPS_PENCIL_PAIR
-#define VPS_PENCIL_PAIR 0
-#endif
-template <int NC>
-constexpr int pencil_pair() {
-  return (NC == 1024 && pencil_tp<NC>() == 8 && (LastRadix<NC>::R % 4) == 0) ? (VPS_PENCIL_PAIR) : 0;
-}
-template <int NC>
-size_t pencil_pair_lds_bytes() {
-  typedef PlanInfo<NC> PI;
-  constexpr size_t ACC = (size_t)8 * 2 * NC, LINES = (size_t)8 * PI::PITCH * 2, IMG = (size_t)(NC / 2) * 16 * 2;
-  const size_t shared = ACC > LINES ? (ACC > IMG ? ACC : IMG) : (LINES > IMG ? LINES : IMG);
-  return shared * sizeof(float) + (size_t)16 * sizeof(cf) + (size_t)(PI::TWLDS ? PI::TW : 0) * sizeof(cf);
-}
-
 template <int NC>
 int launch_pencil(vps_ctx* ctx, const PencilParams& p, long long npencils) {
   typedef PlanInfo<NC> PI;
-  if constexpr (pencil_pair<NC>() != 0) if ((pencil_pair<NC>() & (p.energy ? 2 : 1)) && !p.with_energy && (p.nby % 2) == 0 && npencils % 2 == 0) {
-    const size_t lds2 = pencil_pair_lds_bytes<NC>();
-    auto kern2 = p.energy ? pencil_pair_fft_z_kernel<NC, true> : pencil_pair_fft_z_kernel<NC, false>;
-    if (lds2 > 64 * 1024)
-      VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern2),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    PencilParams pp2 = p;
-    pp2.npencils = (unsigned)npencils;
-    {
-      vps_launch_timer tm(ctx, VPS_K_FFT_Z);
-      hipLaunchKernelGGL(kern2, dim3((unsigned)(npencils / 2)), dim3(8 * pencil_lanes<NC>()), lds2, ctx->stream, pp2);
-    }
-    VPS_HIP_CHECK(ctx, hipGetLastError());
-    return VPS_OK;
-  }
-  if constexpr (pencil_split<NC>()) if (p.energy) {   // (the vector form of the split kernel does not fit 128 VGPRs: whole pencils there)
+  // 2048 packed points (4096-cell lines, where a whole pencil leaves one workgroup per CU), energy launch: the split kernel.
+  // (Its vector form does not fit 128 VGPRs: whole pencils there, as for every other length.)
+  if constexpr (NC == 2048) if (p.energy) {
     const size_t lds2 = pencil_split_lds_bytes<NC>();
     constexpr int TP2 = pencil_tp<NC>();
     auto kern2 = pencil_split_fft_z_kernel<NC, TP2, true>;
@@ -2045,7 +1611,7 @@ int launch_pencil(vps_ctx* ctx, const PencilParams& p, long long npencils) {
     pp2.npencils = (unsigned)npencils;
     {
       vps_launch_timer tm(ctx, VPS_K_FFT_Z);
-      hipLaunchKernelGGL(kern2, dim3((unsigned)npencils), dim3((TP2 / 2) * pencil_lanes<NC>()), lds2, ctx->stream, pp2);
+      hipLaunchKernelGGL(kern2, dim3((unsigned)npencils), dim3((TP2 / 2) * PI::L), lds2, ctx->stream, pp2);
     }
     VPS_HIP_CHECK(ctx, hipGetLastError());
     return VPS_OK;
@@ -2059,16 +1625,9 @@ int launch_pencil(vps_ctx* ctx, const PencilParams& p, long long npencils) {
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   PencilParams pp = p;
   pp.npencils = (unsigned)npencils;
-  long long grid = npencils;
-  if (VPS_PENCIL_PERSIST) {
-    long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const long long want = (long long)ctx->num_cu * per_cu;
-    if (grid > want) grid = want;
-  }
   {
     vps_launch_timer tm(ctx, VPS_K_FFT_Z);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PENCIL_TP * pencil_lanes<NC>()), lds, ctx->stream, pp);
+    hipLaunchKernelGGL(kern, dim3((unsigned)npencils), dim3(PENCIL_TP * PI::L), lds, ctx->stream, pp);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;
@@ -2144,10 +1703,7 @@ constexpr int x_cimg_pitch(bool fast) {   // floats per line of the HELM image: 
   return NC + NC / (fast ? PlanInfo<NC>::RL / 2 : PlanInfo<NC>::RL) + 1;
 }
 template <int NC, int T, int MODE, bool SEG, bool COUNT, int FASTMODE, bool HELM = false>
-#ifndef VPS_X_MIN_WAVES
-#define VPS_X_MIN_WAVES 1
-#endif
-__global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG>() ? (HELM ? 2 : 3) : VPS_X_MIN_WAVES)) fft_x_pass(const XParams p) {
+__global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG>() ? (HELM ? 2 : 3) : 1)) fft_x_pass(const XParams p) {
   typedef PlanInfo<NC> PI;
   constexpr bool FAST = FASTMODE != 0, INTB = FASTMODE == 2, TWREG = x_twreg<NC, FASTMODE, SEG>();
   constexpr int L = PI::L, RL = PI::RL, NT = T * L;
@@ -2404,7 +1960,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
     const float kyp_cur = kyp, kzp_cur = kzp;
     if constexpr (MODE != 0) {
       exchange_sync<WSYNC>();  // previous tile's readers are done with the line buffers
-      fft_from_regs<NC, WSYNC, (TWREG ? 2 : 0)>(v, line, tw, l, twr);
+      fft_from_regs<NC, WSYNC, TWREG>(v, line, tw, l, twr);
     }
     if constexpr (MODE == 1) {
       if (live_cur) {
@@ -2438,23 +1994,10 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
         // opaque copy of the lane index: keeps the LDS / global addresses of this loop from being
         // hoisted out of it as ~50 extra live registers (an occupancy step)
         int lc = l;
-#ifndef VPS_X_NO_OPAQUE
         asm volatile("" : "+v"(lc));
-#endif
         lc = (L & (L - 1)) == 0 ? (lc & (L - 1)) : lc % L;   // give the value range back to the compiler (address folding needs it)
-#ifdef VPS_X_PREFETCH
-        // second register set: the NEXT line set (next component of this tile, or the first of the next tile) is requested
-        // before this one is transformed, so that its loads fly behind the whole transform
-        cf w[RL];
-        if (c + 1 < p.ncomp) {
-          load_line(w, c + 1, lc);
-        } else if (tile + gridDim.x < ntiles) {
-          locate_line(tile + gridDim.x);
-          load_line(w, 0, lc);
-        }
-#endif
         exchange_sync<WSYNC>();  // previous readers are done with the line buffers
-        fft_from_regs<NC, WSYNC, (TWREG ? 2 : 0)>(v, line, tw, lc, twr);
+        fft_from_regs<NC, WSYNC, TWREG>(v, line, tw, lc, twr);
 #pragma unroll
         for (int i = 0; i < RL; ++i) {
           const float a = v[i].x * v[i].x + v[i].y * v[i].y;
@@ -2474,14 +2017,6 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
             dim[i] = (c == 0) ? kc * v[i].y : fmaf(kc, v[i].y, dim[i]);
           }
         }
-#ifdef VPS_X_PREFETCH
-#pragma unroll
-        for (int i = 0; i < RL; ++i) v[i] = w[i];
-        continue;
-#endif
-        // (Requesting the next line BEFORE this transform -- a second register set, affordable at 2048 where LDS limits
-        // the kernel to two waves per SIMD -- was measured at 2048^3: 73.2 against 72.5 ms per step; twiddles and shell
-        // thresholds left in L2 instead of LDS (46 KB: three workgroups per CU instead of two): 73 ms.  Not kept.)
         if (c + 1 < p.ncomp) {
           load_line(v, c + 1, lc);
         } else if (tile + gridDim.x < ntiles) {
@@ -2494,9 +2029,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
       constexpr int CH = FAST ? H : RL;              // chunk length; one pad word per chunk
       {
         int lw = l;   // opaque again: 16 store addresses recomputed per tile instead of kept live
-#ifndef VPS_X_NO_OPAQUE
         asm volatile("" : "+v"(lw));
-#endif
         lw = (L & (L - 1)) == 0 ? (lw & (L - 1)) : lw % L;
 #pragma unroll
         for (int i = 0; i < RL; ++i) {
@@ -2575,11 +2108,7 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
                 if (partner_cur) pc += cr[CIMG + 1];
               }
             }
-#ifdef VPS_ABL_X_NOATOMIC
-            if ((unsigned)bin < (unsigned)p.nbins && pv == 1.2345e30f) {   // TIMING ONLY
-#else
             if ((unsigned)bin < (unsigned)p.nbins) {
-#endif
               if (p.win) pv *= wl[l * H + i];
               atomicAdd(&hsum[bin], (double)(pv * wf));
               if constexpr (HELM) {
@@ -2589,10 +2118,8 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
               if constexpr (COUNT) atomicAdd(&hcnt[bin], c * w);
             }
           };
-#ifndef VPS_ABL_X_NOBIN
 #pragma unroll
           for (int i = 0; i < H; ++i) bin_one(i, INTB ? 0.0 : k2x[INTB ? 0 : i]);
-#endif
           if (l == L - 1) {   // the unpaired kx = NC/2 mode
             int bin;
             if constexpr (INTB) {
@@ -2725,29 +2252,21 @@ constexpr int transpose_T() {
   if (NC <= 2048) return 8;
   return 4;
 }
-// (4096-point lines, L = 256: ONE line per 256-thread workgroup; two lines -- (ky, N-ky) pairs binned together, 512 threads -- measured
-// slower on the C5 rank share: 17.0 against 13.6 ms)
-#ifndef VPS_X_T_LONG
-#define VPS_X_T_LONG 1
-#endif
+// lines per x-pass workgroup: 256 threads' worth (4096-point lines, L = 256: ONE line)
 template <int NC>
 constexpr int xpass_T() {
   constexpr int L = Plan<NC>::L;
-  constexpr int t = (256 / L) > 1 ? (256 / L) : VPS_X_T_LONG;   // (L = 256: 4096-point lines)
+  constexpr int t = (256 / L) > 1 ? (256 / L) : 1;
   return (t > 1 && (t & 1)) ? t - 1 : t;   // even, so that a tile holds whole (ky, N-ky) pairs (L = 50 -> 4)
 }
 
 // lines whose y pass runs the wide kernel (two 8-line groups per workgroup)
 template <int NC>
 constexpr bool wide_transpose() {
-#ifdef VPS_Y_NO_WIDE
-  return false;
-#else
   // 1024: the 16-line tile fits LDS as ONE 1024-thread workgroup per CU (1.80 ms per 1024^3 launch); as two groups of 8 it is
   // two persistent 512-thread workgroups per CU: 1.58 ms.  512 (32 lines, 256-byte segments): 0.20 -> 0.21 ms, not taken.
   // 2000: 800 threads x 2 x 20 points do not fit 128 VGPRs.
   return NC == 1024 || NC == 1536 || NC == 2048 || NC == 4096;
-#endif
 }
 
 template <int NC, int T>
@@ -2914,23 +2433,24 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
 #define VPS_PARTFN(name) VPS_CAT(VPS_CAT(name, _p), VPS_FFT_PART)
 #endif
 
+#define VPS_CASE(N, CALL) case N: { constexpr int NC_ = N; CALL; } break;
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 0
-#define VPS_FAMILY_0(CALL) case 8: { constexpr int NC_ = 8; CALL; } break; case 16: { constexpr int NC_ = 16; CALL; } break; case 32: { constexpr int NC_ = 32; CALL; } break; case 64: { constexpr int NC_ = 64; CALL; } break; case 128: { constexpr int NC_ = 128; CALL; } break; case 256: { constexpr int NC_ = 256; CALL; } break;
+#define VPS_FAMILY_0(CALL) VPS_CASE(8, CALL) VPS_CASE(16, CALL) VPS_CASE(32, CALL) VPS_CASE(64, CALL) VPS_CASE(128, CALL) VPS_CASE(256, CALL)
 #else
 #define VPS_FAMILY_0(CALL)
 #endif
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 1
-#define VPS_FAMILY_1(CALL) case 512: { constexpr int NC_ = 512; CALL; } break; case 1024: { constexpr int NC_ = 1024; CALL; } break; case 2048: { constexpr int NC_ = 2048; CALL; } break; case 4096: { constexpr int NC_ = 4096; CALL; } break;
+#define VPS_FAMILY_1(CALL) VPS_CASE(512, CALL) VPS_CASE(1024, CALL) VPS_CASE(2048, CALL) VPS_CASE(4096, CALL)
 #else
 #define VPS_FAMILY_1(CALL)
 #endif
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 2
-#define VPS_FAMILY_2(CALL) case 48: { constexpr int NC_ = 48; CALL; } break; case 96: { constexpr int NC_ = 96; CALL; } break; case 192: { constexpr int NC_ = 192; CALL; } break; case 384: { constexpr int NC_ = 384; CALL; } break; case 768: { constexpr int NC_ = 768; CALL; } break; case 1536: { constexpr int NC_ = 1536; CALL; } break;
+#define VPS_FAMILY_2(CALL) VPS_CASE(48, CALL) VPS_CASE(96, CALL) VPS_CASE(192, CALL) VPS_CASE(384, CALL) VPS_CASE(768, CALL) VPS_CASE(1536, CALL)
 #else
 #define VPS_FAMILY_2(CALL)
 #endif
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 3
-#define VPS_FAMILY_3(CALL) case 125: { constexpr int NC_ = 125; CALL; } break; case 250: { constexpr int NC_ = 250; CALL; } break; case 500: { constexpr int NC_ = 500; CALL; } break; case 1000: { constexpr int NC_ = 1000; CALL; } break; case 2000: { constexpr int NC_ = 2000; CALL; } break;
+#define VPS_FAMILY_3(CALL) VPS_CASE(125, CALL) VPS_CASE(250, CALL) VPS_CASE(500, CALL) VPS_CASE(1000, CALL) VPS_CASE(2000, CALL)
 #else
 #define VPS_FAMILY_3(CALL)
 #endif
@@ -2969,17 +2489,17 @@ void build_stage_tw(std::vector<cf>& out) {
 
 // ---- per-part entry points (this unit's line lengths; VPS_PART_NOT_MINE for the others) ----
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 0
-#define VPS_PENCIL_FAMILY_0(CALL) case 32: { constexpr int NC_ = 32; CALL; } break; case 64: { constexpr int NC_ = 64; CALL; } break; case 128: { constexpr int NC_ = 128; CALL; } break; case 256: { constexpr int NC_ = 256; CALL; } break;
+#define VPS_PENCIL_FAMILY_0(CALL) VPS_CASE(32, CALL) VPS_CASE(64, CALL) VPS_CASE(128, CALL) VPS_CASE(256, CALL)
 #else
 #define VPS_PENCIL_FAMILY_0(CALL)
 #endif
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 1
-#define VPS_PENCIL_FAMILY_1(CALL) case 512: { constexpr int NC_ = 512; CALL; } break; case 1024: { constexpr int NC_ = 1024; CALL; } break; case 2048: { constexpr int NC_ = 2048; CALL; } break;
+#define VPS_PENCIL_FAMILY_1(CALL) VPS_CASE(512, CALL) VPS_CASE(1024, CALL) VPS_CASE(2048, CALL)
 #else
 #define VPS_PENCIL_FAMILY_1(CALL)
 #endif
 #if VPS_FFT_PART == -1 || VPS_FFT_PART == 2
-#define VPS_PENCIL_FAMILY_2(CALL) case 96: { constexpr int NC_ = 96; CALL; } break; case 192: { constexpr int NC_ = 192; CALL; } break; case 384: { constexpr int NC_ = 384; CALL; } break; case 768: { constexpr int NC_ = 768; CALL; } break;
+#define VPS_PENCIL_FAMILY_2(CALL) VPS_CASE(96, CALL) VPS_CASE(192, CALL) VPS_CASE(384, CALL) VPS_CASE(768, CALL)
 #else
 #define VPS_PENCIL_FAMILY_2(CALL)
 #endif
@@ -3395,7 +2915,7 @@ static int fft_y_of(vps_ctx* ctx, int N, int nx, const cf* B, const cf* BN, void
   return rc;
 }
 
-int vps_pencil_tp(int N) { return N / 2 >= 1024 ? VPS_PENCIL_TP_LONG : 16; }   // = pencil_tp<N/2>()
+int vps_pencil_tp(int N) { return N / 2 >= 1024 ? 8 : 16; }   // = pencil_tp<N/2>()
 
 bool vps_pencil_supported(vps_ctx* ctx, int N) {
   if (!vps_fft_supported(N) || N < 64 || N > 4096) return false;   // (4096: 8-line pencils of 2048 packed points on 1024 threads, 148 KB of LDS)
