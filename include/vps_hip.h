@@ -43,7 +43,8 @@ enum vps_status {
 
 /* quantities of BoxField.spctrm (interp.py:573-583) */
 enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
-                    VPS_VM = 3 /* BoxField form: v in channels 0..2, mass in channel 3 */ };
+                    VPS_VM = 3 /* BoxField form: v in channels 0..2, mass in channel 3 */,
+                    VPS_WEIGHTED_VELOCITY = 4 /* ABI 8: w = rho^alpha v, alpha from vps_set_density_weight (below) */ };
 /* flags for vps_field_algebra */
 #define VPS_FLAG_REFERENCE_MOMENTUM_BUG 1 /* py=pz=vx*mass as interp.py:523-525 */
 #define VPS_FLAG_INPUT_IS_VM 2             /* channels already hold vx,vy,vz,mass (a BoxField) */
@@ -74,7 +75,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 7
+#define VPS_ABI_VERSION 8
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -96,6 +97,20 @@ int vps_device_info(vps_ctx* ctx, int64_t out[4]);
  * ix^2 + iy^2 + iz^2 against integer thresholds (exactly the same shells: chosen only where vps_set_binning has checked
  * that no threshold lies on an integer multiple of k2[1]); negative: no tables set */
 int vps_binning_mode(vps_ctx* ctx);
+
+/* Density-weighted velocity (ABI 8; an extension, the reference has no such quantity): VPS_WEIGHTED_VELOCITY is the vector
+ * field w_c = rho^alpha v_c = (sum rho v_c) rho^(alpha - 1) with rho the cell's density total (NGP) or the nearest particle's
+ * density (exact NN), rho = mass / Lcell^3 for a gridded field (VPS_FLAG_INPUT_IS_VM); w = 0 where rho = 0 for EVERY alpha,
+ * 0 included.  alpha = 1/3: the scaling variable of supersonic turbulence; 1/2: the spectrum that integrates to the kinetic
+ * energy density; alpha = 0 is VPS_VELOCITY and alpha = 1 is VPS_MOMENTUM / Lcell^3 (to float32 rounding: the power is formed
+ * as exp2((alpha - 1) log2 rho) on the hardware units where VPS_VELOCITY takes a reciprocal).
+ * vps_set_density_weight stores alpha (any finite double; else VPS_ERR_ARG) on the context, like vps_set_window; it is read
+ * when a call is enqueued.  The quantity is taken by vps_deposit_field, vps_deposit_fft_zy[_supported], vps_deposit_fft_z[_slab],
+ * vps_nn_resample_quantity, vps_field_algebra[_out]: three output channels, VPS_FLAG_COMPONENTS and VPS_FLAG_REUSE_SORT as for
+ * VPS_VELOCITY.  VPS_ERR_ARG, before anything is enqueued: the quantity on a context whose alpha was never set; with
+ * VPS_FLAG_SHARE_ENERGY or VPS_FLAG_REFERENCE_MOMENTUM_BUG.  Outside the contract: densities that are float32 denormals or
+ * negative, and powers rho^(alpha - 1) (rho^alpha for gridded input) beyond the float32 range. */
+int vps_set_density_weight(vps_ctx* ctx, double alpha);
 
 /* ---- memory helpers (so the library is usable without torch) ------------ */
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);

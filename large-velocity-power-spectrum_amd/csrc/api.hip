@@ -395,4 +395,20 @@ int vps_set_window(vps_ctx* ctx, int N, const float* inv_w2_axis_host) {
   return VPS_OK;
 }
 
+int vps_set_density_weight(vps_ctx* ctx, double alpha) {
+  VPS_ENTER(ctx);
+  if (!std::isfinite(alpha)) return vps_fail(ctx, VPS_ERR_ARG, "vps_set_density_weight: alpha must be finite");
+  ctx->weight_alpha = alpha;   // host state only: read when a VPS_WEIGHTED_VELOCITY call is enqueued
+  return VPS_OK;
+}
+
 }  // extern "C"
+
+int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags) {
+  if (quantity != VPS_WEIGHTED_VELOCITY) return VPS_OK;
+  if (!std::isfinite(ctx->weight_alpha))
+    return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_WEIGHTED_VELOCITY without an exponent (vps_set_density_weight)", who);
+  if (flags & (VPS_FLAG_SHARE_ENERGY | VPS_FLAG_REFERENCE_MOMENTUM_BUG))
+    return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_WEIGHTED_VELOCITY takes neither VPS_FLAG_SHARE_ENERGY nor VPS_FLAG_REFERENCE_MOMENTUM_BUG", who);
+  return VPS_OK;
+}

@@ -659,7 +659,29 @@ __device__ __forceinline__ void algebra_cell(float a, float b, float c, float rh
   }
 }
 
-// QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count
+// Density-weighted velocity w = rho^alpha v (VPS_WEIGHTED_VELOCITY), 0 where there is no mass whatever alpha is.  The power is
+// exp2(e log2 rho) on the transcendental units (v_log_f32, v_exp_f32), as in the pencil kernel (fft.hip: pencil_rho_factor):
+//   channels [rho v, rho]:               w = (rho v) rho^(alpha - 1)
+//   VPS_FLAG_INPUT_IS_VM [v, mass]:      w = v (mass / vol)^alpha
+// A function of its own: algebra_cell and the kernels built on it stay what they were.
+__device__ __forceinline__ void weighted_cell(float a, float b, float c, float rho, int flags, float vol, float alpha,
+                                              float out[4]) {
+  float f;
+  if (flags & VPS_FLAG_INPUT_IS_VM) {
+    const float r = rho * __builtin_amdgcn_rcpf(vol);
+    f = rho != 0.f ? __builtin_amdgcn_exp2f(alpha * __builtin_amdgcn_logf(r)) : 0.f;
+  } else {
+    f = rho != 0.f ? __builtin_amdgcn_exp2f((alpha - 1.f) * __builtin_amdgcn_logf(rho)) : 0.f;
+  }
+  // (a zero factor must give 0, not NaN, for whatever the empty cell's velocity channels hold)
+  out[0] = f != 0.f ? a * f : 0.f;
+  out[1] = f != 0.f ? b * f : 0.f;
+  out[2] = f != 0.f ? c * f : 0.f;
+  out[3] = 0.f;
+}
+
+// QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count.
+// QUANT == VPS_WEIGHTED_VELOCITY: `vol` carries alpha instead (the epilogue needs no cell volume: rho is channel 3 itself).
 template <int C, int EPI, int QUANT>
 __global__ void __launch_bounds__(256)
     brick_accumulate_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start,
@@ -738,10 +760,17 @@ __global__ void __launch_bounds__(256)
           *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
           if (inside) {
             float rx[4], ry[4], rz[4], rw[4];
-            algebra_cell(c0.x, c1.x, c2.x, c3.x, quantity, flags, vol, rx);
-            algebra_cell(c0.y, c1.y, c2.y, c3.y, quantity, flags, vol, ry);
-            algebra_cell(c0.z, c1.z, c2.z, c3.z, quantity, flags, vol, rz);
-            algebra_cell(c0.w, c1.w, c2.w, c3.w, quantity, flags, vol, rw);
+            if constexpr (QUANT == VPS_WEIGHTED_VELOCITY) {
+              weighted_cell(c0.x, c1.x, c2.x, c3.x, 0, 1.f, vol, rx);
+              weighted_cell(c0.y, c1.y, c2.y, c3.y, 0, 1.f, vol, ry);
+              weighted_cell(c0.z, c1.z, c2.z, c3.z, 0, 1.f, vol, rz);
+              weighted_cell(c0.w, c1.w, c2.w, c3.w, 0, 1.f, vol, rw);
+            } else {
+              algebra_cell(c0.x, c1.x, c2.x, c3.x, quantity, flags, vol, rx);
+              algebra_cell(c0.y, c1.y, c2.y, c3.y, quantity, flags, vol, ry);
+              algebra_cell(c0.z, c1.z, c2.z, c3.z, quantity, flags, vol, rz);
+              algebra_cell(c0.w, c1.w, c2.w, c3.w, quantity, flags, vol, rw);
+            }
 #pragma unroll
             for (int c = 0; c < NOUT; ++c)
               {   // streaming store: the grid is written once; the cache should keep the records (-33 %)
@@ -769,7 +798,10 @@ __global__ void __launch_bounds__(256)
           for (int c = 0; c < C; ++c) grid[c * plane + cell] = v[c];
         } else {
           float r[4];
-          algebra_cell(v[0], v[1], v[2], v[3], quantity, flags, vol, r);
+          if constexpr (QUANT == VPS_WEIGHTED_VELOCITY)
+            weighted_cell(v[0], v[1], v[2], v[3], 0, 1.f, vol, r);
+          else
+            algebra_cell(v[0], v[1], v[2], v[3], quantity, flags, vol, r);
 #pragma unroll
           for (int c = 0; c < NOUT; ++c) grid[c * plane + cell] = r[c];
         }
@@ -807,6 +839,31 @@ __global__ void __launch_bounds__(256)
     *reinterpret_cast<float4*>(dst + 2 * ncell + i0) = c;
   }
   if (quantity == VPS_VM) *reinterpret_cast<float4*>(dst + 3 * ncell + i0) = m;
+}
+
+// The density-weighted velocity of a gridded field (vps_field_algebra[_out] with VPS_WEIGHTED_VELOCITY): three channels,
+// in place or to `out`; a kernel of its own, so that field_algebra_kernel is untouched.
+__global__ void __launch_bounds__(256)
+    field_weighted_kernel(float* ch, long long ncell, int flags, float vol, float alpha, float* out) {
+  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i0 >= ncell) return;
+  float* dst = out ? out : ch;
+  float4 a = *reinterpret_cast<float4*>(ch + i0);
+  float4 b = *reinterpret_cast<float4*>(ch + ncell + i0);
+  float4 c = *reinterpret_cast<float4*>(ch + 2 * ncell + i0);
+  const float4 m = *reinterpret_cast<float4*>(ch + 3 * ncell + i0);
+  float r[4];
+  weighted_cell(a.x, b.x, c.x, m.x, flags, vol, alpha, r);
+  a.x = r[0]; b.x = r[1]; c.x = r[2];
+  weighted_cell(a.y, b.y, c.y, m.y, flags, vol, alpha, r);
+  a.y = r[0]; b.y = r[1]; c.y = r[2];
+  weighted_cell(a.z, b.z, c.z, m.z, flags, vol, alpha, r);
+  a.z = r[0]; b.z = r[1]; c.z = r[2];
+  weighted_cell(a.w, b.w, c.w, m.w, flags, vol, alpha, r);
+  a.w = r[0]; b.w = r[1]; c.w = r[2];
+  *reinterpret_cast<float4*>(dst + i0) = a;
+  *reinterpret_cast<float4*>(dst + ncell + i0) = b;
+  *reinterpret_cast<float4*>(dst + 2 * ncell + i0) = c;
 }
 
 // [rho vx, rho vy, rho vz, rho] per particle (interp.py:199-213)
@@ -1147,6 +1204,12 @@ int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const flo
     if (EPI == EPI_RAW || quantity == VPS_VELOCITY) VPS_BRICK(VPS_VELOCITY);
     else if (quantity == VPS_MOMENTUM) VPS_BRICK(VPS_MOMENTUM);
     else if (quantity == VPS_ENERGY) VPS_BRICK(VPS_ENERGY);
+    else if (quantity == VPS_WEIGHTED_VELOCITY) {
+      if constexpr (EPI == EPI_ALGEBRA) {   // (the kernel's float argument is alpha here, see brick_accumulate_kernel)
+        hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, VPS_WEIGHTED_VELOCITY>), dim3((unsigned)grid_wg), dim3(256), lds,
+                           ctx->stream, records, start, b, l.nbricks, flags, (float)ctx->weight_alpha, grid);
+      }
+    }
     else VPS_BRICK(VPS_VM);
 #undef VPS_BRICK
   }
@@ -1245,7 +1308,8 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   VPS_ENTER(ctx);
   int rc = check_deposit_args(ctx, "vps_deposit_field", np, N, Lbox, x0, nx);
   if (rc) return rc;
-  if (quantity < 0 || quantity > 3) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
+  if (quantity < 0 || quantity > VPS_WEIGHTED_VELOCITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
+  if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
   if (flags & VPS_FLAG_INPUT_IS_VM) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_INPUT_IS_VM is meaningless here");
   if (!fields_dev || !work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: null buffer");
@@ -1257,7 +1321,8 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
 
 int vps_deposit_fft_zy_supported(vps_ctx* ctx, int N, int quantity) {
   if (!ctx) return 0;
-  return (quantity == VPS_VELOCITY || quantity == VPS_MOMENTUM || quantity == VPS_ENERGY) && vps_pencil_supported(ctx, N) ? 1 : 0;
+  return (quantity == VPS_VELOCITY || quantity == VPS_MOMENTUM || quantity == VPS_ENERGY || quantity == VPS_WEIGHTED_VELOCITY) &&
+                 vps_pencil_supported(ctx, N) ? 1 : 0;
 }
 
 size_t vps_deposit_fft_zy_workspace_bytes(int64_t np, int N, int nx) {
@@ -1352,6 +1417,7 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   if (rc) return rc;
   if (!vps_deposit_fft_zy_supported(ctx, N, quantity))
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_fft_zy: N=%d quantity=%d not supported by the fused path", N, quantity);
+  if ((rc = vps_check_weighted(ctx, "vps_deposit_fft_zy", quantity, flags))) return rc;
   if (!work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_fft_zy: null buffer");
   const Bricks b = make_pencils(N, x0, nx, vps_pencil_tp(N));
@@ -1387,7 +1453,9 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   return vps_fft_pencil_zy(ctx, N, nx, reinterpret_cast<const unsigned*>(work + l.records),
                            reinterpret_cast<const unsigned*>(work + l.start), reinterpret_cast<float*>(work + l.ranks), ncomp, chan,
                            quantity == VPS_MOMENTUM ? 0 : 1, quantity == VPS_ENERGY ? 1 : 0, (float)(lc * lc * lc),
-                           spec_dev, nyq_dev, zimg_dev ? zimg_dev : (void*)(work + l.total), with_energy);
+                           spec_dev, nyq_dev, zimg_dev ? zimg_dev : (void*)(work + l.total), with_energy,
+                           quantity == VPS_WEIGHTED_VELOCITY ? 1 : 0,
+                           quantity == VPS_WEIGHTED_VELOCITY ? (float)(ctx->weight_alpha - 1.0) : 0.f);
 }
 
 int vps_density_velocity_vector(vps_ctx* ctx, const float* vel_dev, const float* rho_dev, int64_t np,
@@ -1442,7 +1510,8 @@ int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell, float
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,
                           int64_t ncell, float* out_dev) {
   VPS_ENTER(ctx);
-  if (quantity < 0 || quantity > 3) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (quantity < 0 || quantity > VPS_WEIGHTED_VELOCITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;
   if (ncell < 0 || (ncell & 3)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: ncell must be a multiple of 4");
   if (ncell == 0) return VPS_OK;
   if (!chans_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: null buffer");
@@ -1450,8 +1519,12 @@ int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, c
   const unsigned blocks = (unsigned)((nthreads + 255) / 256);
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
-    hipLaunchKernelGGL(field_algebra_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
-                       (long long)ncell, quantity, flags, (float)(Lcell * Lcell * Lcell), out_dev);
+    if (quantity == VPS_WEIGHTED_VELOCITY)
+      hipLaunchKernelGGL(field_weighted_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
+                         (long long)ncell, flags, (float)(Lcell * Lcell * Lcell), (float)ctx->weight_alpha, out_dev);
+    else
+      hipLaunchKernelGGL(field_algebra_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
+                         (long long)ncell, quantity, flags, (float)(Lcell * Lcell * Lcell), out_dev);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;

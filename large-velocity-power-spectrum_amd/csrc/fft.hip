@@ -1026,6 +1026,7 @@ struct PencilParams {
   int ncomp;
   int chan[3];               // record channel (0..2) feeding component c
   int divide;                // 1: v = q / rho (0 where rho == 0);  0: p = q * vol
+                             // (divide = 1 with `weighted`: w = q * rho^wexp, the density-weighted velocity rho^alpha v)
   int energy;                // 1: ONE output field E = vol * sum_c q_c^2 / rho (= mass * |v|^2, interp.py:546)
   int with_energy;           // momentum launch (divide = 0, three components) that ALSO writes the energy field as out[3]: the
                              // cell totals of rho v_c its rounds accumulate are what E is made of -- one more round (rho) and
@@ -1036,10 +1037,26 @@ struct PencilParams {
   cf* nyq[4];                // BN_c[x][y]
   const cf* tw_stage;
   const cf* tw_r2c;
+  // density-weighted velocity (VPS_WEIGHTED_VELOCITY; last, so that no other member moves): the WEIGHTED instantiation keeps
+  // rho^wexp, wexp = alpha - 1, per record where the velocity form keeps 1 / rho
+  int weighted;
+  float wexp;
 };
 
+// The per-record factor of the dividing launches: 1 / rho (v_rcp_f32), or for the density-weighted velocity rho^(alpha - 1) as
+// exp2((alpha - 1) log2 rho) on the transcendental units (v_log_f32, one multiply, v_exp_f32: once per record and launch, outside
+// every round).  Empty cells give 0 for every alpha (the NaN -> 0 rule of interp.py:329-331).  rho is a sum of positive
+// densities; float32 denormals and powers beyond the float32 range are outside the contract (include/vps_hip.h).
+template <bool WEIGHTED>
+__device__ __forceinline__ float pencil_rho_factor(float r, float wexp) {
+  if constexpr (WEIGHTED)
+    return r != 0.f ? __builtin_amdgcn_exp2f(wexp * __builtin_amdgcn_logf(r)) : 0.f;
+  else
+    return r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
+}
+
 // One workgroup per pencil, on the plan's lanes per line; four waves per SIMD (measured at 512^3 / 1024^3 / 2048^3) need <= 128 VGPRs.
-template <int NC, int TP, bool ENERGY = false>
+template <int NC, int TP, bool ENERGY = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(const PencilParams p) {
   typedef PlanInfo<NC> PI;
   constexpr int L = PI::L, RL = PI::RL, NT = TP * L, N = 2 * NC;
@@ -1083,7 +1100,7 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
   constexpr int KR = NT >= 512 ? 2 : (NT >= 256 ? 3 : 4);
   unsigned rloc[KR];
   float rval[KR];
-  float rrec[KR];   // 1/rho of the record's cell (velocity) / sum over components of (rho v_c)^2 of its cell (ENERGY)
+  float rrec[KR];   // 1/rho of the record's cell (velocity; WEIGHTED: rho^(alpha-1)) / sum over components of (rho v_c)^2 of its cell (ENERGY)
   auto fetch = [&](int word) {   // record word 1..3: rho v_c, 4: rho
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
@@ -1123,11 +1140,11 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
     for (int k = 0; k < KR; ++k)
       if (rloc[k] != 0xffffffffu) {
         const float r = acc[rloc[k]];
-        rrec[k] = r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
+        rrec[k] = pencil_rho_factor<WEIGHTED>(r, p.wexp);
       }
     for (unsigned j = tail0; j < e; j += NT) {
       const float r = acc[p.records[(size_t)j * 5]];
-      p.side[j] = r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
+      p.side[j] = pencil_rho_factor<WEIGHTED>(r, p.wexp);
     }
   }
 
@@ -1619,7 +1636,8 @@ int launch_pencil(vps_ctx* ctx, const PencilParams& p, long long npencils) {
   const size_t lds = pencil_lds_bytes<NC>();
   constexpr int PENCIL_TP = pencil_tp<NC>();
   if (lds > ctx->lds_per_cu) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "pencil kernel needs %zu B LDS", lds);
-  auto kern = p.energy ? pencil_fft_z_kernel<NC, PENCIL_TP, true> : pencil_fft_z_kernel<NC, PENCIL_TP, false>;
+  auto kern = p.energy ? pencil_fft_z_kernel<NC, PENCIL_TP, true>
+                       : (p.weighted ? pencil_fft_z_kernel<NC, PENCIL_TP, false, true> : pencil_fft_z_kernel<NC, PENCIL_TP, false>);
   if (lds > 64 * 1024)
     VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2928,7 +2946,9 @@ bool vps_pencil_supported(vps_ctx* ctx, int N) {
 // z images [component][B | BN] stay in bwork_dev)
 int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, const unsigned* start, float* side,
                       int ncomp, const int* chan, int divide, int energy, float vol, void* spec_dev, void* nyq_dev,
-                      void* bwork_dev, int with_energy) {
+                      void* bwork_dev, int with_energy, int weighted, float wexp) {
+  if (weighted && (!divide || energy || with_energy))
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_pencil_zy: the density-weighted velocity is a dividing vector launch of its own");
   // with_energy = 1: a momentum launch (three components) that leaves the energy field's z image as component 3 of bwork_dev;
   // with_energy = 2: no launch -- the y pass of that component 3 (the energy quantity of a step whose momentum launch made it)
   if (with_energy && (energy != (with_energy == 2) || divide != (with_energy == 2 ? 1 : 0) || (with_energy == 1 && ncomp != 3)))
@@ -2955,6 +2975,8 @@ int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, cons
   p.divide = divide;
   p.energy = energy;
   p.with_energy = with_energy == 1;
+  p.weighted = weighted;
+  p.wexp = wexp;
   p.vol = vol;
   p.tw_stage = tz.tw_stage;
   p.tw_r2c = tz.tw_r2c;

@@ -72,6 +72,9 @@ struct vps_ctx {
   double* d_axes = nullptr;
   size_t axes_cap = 0;
 
+  // exponent alpha of the density-weighted velocity rho^alpha v (vps_set_density_weight); NaN: never set
+  double weight_alpha = __builtin_nan("");
+
   vps_comm* comm = nullptr;      // vps_comm_create
 
   unsigned nn_open_points = 0;   // diagnostics: lattice points the last NN scatter pass left to the exact fallback
@@ -84,6 +87,10 @@ struct vps_ctx {
 int vps_fail(vps_ctx* ctx, int code, const char* fmt, ...);
 // Tuning / test switches set by the host through vps_set_option (process-wide; the library never reads the environment).
 double vps_option(const char* name, double dflt);
+
+// VPS_WEIGHTED_VELOCITY needs an exponent on the context and takes neither VPS_FLAG_SHARE_ENERGY nor
+// VPS_FLAG_REFERENCE_MOMENTUM_BUG: VPS_ERR_ARG, checked at the entry points before anything is enqueued (api.hip)
+int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags);
 
 // Every entry point of the C ABI runs with the context's device current and restores the caller's
 // on return: the library allocates (tables, partial sums, lattice axes) and launches on streams
@@ -131,7 +138,7 @@ bool vps_pencil_supported(vps_ctx* ctx, int N);
 // side: one float per record (scratch of the kernel: what it keeps per record when a bucket outgrows its registers)
 int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, const unsigned* start, float* side,
                       int ncomp, const int* chan, int divide, int energy, float vol, void* spec_dev, void* nyq_dev,
-                      void* bwork_dev, int with_energy = 0);
+                      void* bwork_dev, int with_energy = 0, int weighted = 0, float wexp = 0.f);   // weighted: q * rho^wexp
 
 // ---- LDS floating-point accumulation ---------------------------------------------------------
 // gfx950 executes ds_add_f32 far below the LDS rate (measured: about one lane every two clocks per

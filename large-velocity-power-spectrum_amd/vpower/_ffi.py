@@ -69,6 +69,7 @@ SYMBOLS = (
     ("vps_set_binning", C.c_int, (_vp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double)),
     ("vps_set_bin_only", C.c_int, (_vp, C.c_int)),
     ("vps_set_window", C.c_int, (_vp, C.c_int, _vp)),
+    ("vps_set_density_weight", C.c_int, (_vp, C.c_double)),
     ("vps_assign_expand", C.c_int, (_vp, _vp, C.c_int, _vp, _i64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp)),
     ("vps_fft_workspace_bytes", C.c_size_t, (C.c_int, C.c_int)),
     ("vps_fft_zy", C.c_int, (_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp)),
@@ -116,7 +117,7 @@ KERNEL_KINDS = {"deposit": K_DEPOSIT, "algebra": K_ALGEBRA, "fft_z": K_FFT_Z, "f
                 "exchange": K_EXCHANGE, "exchange_wait": K_EXCHANGE_WAIT}
 
 
-ABI_VERSION = 7   # include/vps_hip.h: VPS_ABI_VERSION
+ABI_VERSION = 8   # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

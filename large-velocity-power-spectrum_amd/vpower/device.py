@@ -28,12 +28,73 @@ import torch
 
 from . import _ffi
 
-VELOCITY, MOMENTUM, ENERGY, VM = 0, 1, 2, 3
-QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY}
+VELOCITY, MOMENTUM, ENERGY, VM, WEIGHTED = 0, 1, 2, 3, 4
+QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED}
 FLAG_REFERENCE_MOMENTUM_BUG = 1
 FLAG_INPUT_IS_VM = 2
 FLAG_REUSE_SORT = 4
 FLAG_SHARE_ENERGY = 8
+NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3}      # output channels of a quantity
+
+
+class WeightedVelocity(int):
+    """The quantity code of the density-weighted velocity w = rho^alpha v (VPS_WEIGHTED_VELOCITY = 4) TOGETHER with its
+    exponent: an int, so that it goes wherever a quantity code goes (int(q), the C calls), and the kernels
+    wrapper hands `alpha` to the library (vps_set_density_weight) right before every call that forms the field -- the
+    context's exponent is never what an earlier field left there."""
+
+    def __new__(cls, alpha):
+        alpha = float(alpha)
+        if not np.isfinite(alpha):
+            raise ValueError("density_weight must be a finite number, got %r" % (alpha,))
+        self = super().__new__(cls, WEIGHTED)
+        self.alpha = alpha
+        return self
+
+    # As a KEY the exponent counts: two weighted quantities are equal only when their exponents are, and none equals the
+    # bare code 4 -- a table, set or cache keyed by quantity keeps rho^(1/3) v and rho^(1/2) v apart.  Code that asks "is
+    # this the weighted quantity" compares int(q) == WEIGHTED.
+    def __eq__(self, other):
+        return isinstance(other, WeightedVelocity) and self.alpha == other.alpha
+
+    def __ne__(self, other):
+        return not self.__eq__(other)
+
+    def __hash__(self):
+        return hash((WEIGHTED, self.alpha))
+
+    def __repr__(self):
+        return "WeightedVelocity(alpha=%r)" % self.alpha
+
+
+# names BoxField.spctrm / helmholtz_spctrm take for the density-weighted velocity with a fixed exponent
+WEIGHT_SHORTHANDS = {"rho13_velocity": 1.0 / 3.0, "rho12_velocity": 0.5}
+VECTOR_QUANTITIES = ("velocity", "momentum", "weighted_velocity") + tuple(WEIGHT_SHORTHANDS)
+
+
+def resolve_quantity(quantity, density_weight=None, supported=None):
+    """(name, code) of a quantity name of BoxField.spctrm: name is 'velocity' | 'momentum' | 'energy' | 'weighted_velocity',
+    code the library's (a WeightedVelocity carrying alpha for the last).  'weighted_velocity' needs density_weight = alpha
+    (finite); 'rho13_velocity' / 'rho12_velocity' are alpha = 1/3 and 1/2; density_weight with any other name is an error.
+    `supported` restricts the names (the Helmholtz decomposition: vector quantities)."""
+    names = tuple(QUANTITY) + tuple(WEIGHT_SHORTHANDS)
+    if supported is not None:
+        names = tuple(n for n in names if n in supported)
+    if not isinstance(quantity, str) or quantity not in names:
+        raise Exception("""Unrecognized physical quantity name.
+        Supported%s: %s.""" % ("" if supported is None else " here", ", ".join(repr(n) for n in names)))
+    if quantity in WEIGHT_SHORTHANDS:
+        if density_weight is not None:
+            raise ValueError("density_weight is implied by %r (alpha = %g); pass it with 'weighted_velocity' only"
+                             % (quantity, WEIGHT_SHORTHANDS[quantity]))
+        return "weighted_velocity", WeightedVelocity(WEIGHT_SHORTHANDS[quantity])
+    if quantity == "weighted_velocity":
+        if density_weight is None:
+            raise ValueError("quantity 'weighted_velocity' needs density_weight=alpha (w = rho^alpha v)")
+        return quantity, WeightedVelocity(density_weight)
+    if density_weight is not None:
+        raise ValueError("density_weight only goes with quantity 'weighted_velocity', not %r" % (quantity,))
+    return quantity, QUANTITY[quantity]
 
 
 # --------------------------------------------------------------------------- #
@@ -288,10 +349,20 @@ class HipKernels:
                                            float(Lbox), x0, nx, self._ptr(out, torch.float32), self._ptr(work)))
         return out
 
+    def _set_weight(self, quantity):
+        """Before a call that forms the fields of `quantity`: a weighted quantity's exponent goes to the context NOW."""
+        if int(quantity) == WEIGHTED:
+            alpha = getattr(quantity, "alpha", None)
+            if alpha is None:
+                raise Exception("the density-weighted velocity needs its exponent: pass device.WeightedVelocity(alpha)")
+            self._chk(self.lib.vps_set_density_weight(self.ctx, float(alpha)))
+        return int(quantity)
+
     def deposit_field(self, pos, vel, rho, N, Lbox, x0, nx, quantity, flags=0, out=None):
         """Fused deposit of [rho v, rho] + field algebra -> [ncomp, nx, N, N] float32."""
         self._stream()
-        ncomp = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4}[quantity]
+        quantity = self._set_weight(quantity)
+        ncomp = NCOMP[quantity]
         if out is None:
             out = self.empty((ncomp, nx, N, N), torch.float32)
         work = self.workspace("deposit", self.lib.vps_deposit_workspace_bytes(pos.shape[0], 4, N, nx))
@@ -315,7 +386,8 @@ class HipKernels:
         made of -- leaves that field's z image there as well (VPS_FLAG_SHARE_ENERGY), and the energy call that follows it with a
         valid reuse_sort token only runs its y pass.  Any other order of calls simply launches the energy kernel as usual."""
         self._stream()
-        ncomp = 1 if quantity == ENERGY else 3
+        quantity = self._set_weight(quantity)
+        ncomp = NCOMP[quantity]
         if component is not None:
             mask = self._component_mask(quantity, component)
             flags |= mask << 4
@@ -352,7 +424,7 @@ class HipKernels:
         """component: 0..2 or a collection of them -> the bit mask of VPS_FLAG_COMPONENTS."""
         comps = (component,) if isinstance(component, (int, np.integer)) else tuple(component)
         if quantity == ENERGY or not comps or any(not 0 <= int(c) <= 2 for c in comps) or len(set(comps)) != len(comps):
-            raise Exception("component(s) = distinct values 0..2 of a velocity or momentum field")
+            raise Exception("component(s) = distinct values 0..2 of a velocity, momentum or weighted-velocity field")
         mask = 0
         for c in comps:
             mask |= 1 << int(c)
@@ -414,10 +486,11 @@ class HipKernels:
     def nn_resample_quantity(self, pos, rhov, axes, x0, nx, Lcell, quantity, flags=0, out=None, want_index=False):
         """Exact-NN resampling of [rho v, rho] straight into the fields the spectrum of `quantity` transforms
         (vps_nn_resample_quantity): VELOCITY -> [3, ...] v; MOMENTUM -> [3, ...] p = v * mass; ENERGY -> [1, ...] mass |v|^2;
-        VM -> [4, ...] (= nn_resample_field)."""
+        VM -> [4, ...] (= nn_resample_field); a WeightedVelocity -> [3, ...] rho^alpha v of the nearest particle."""
         self._stream()
+        quantity = self._set_weight(quantity)
         ax = [np.ascontiguousarray(a, dtype=np.float64) for a in axes]
-        nout = 1 if quantity == ENERGY else (4 if quantity == VM else 3)
+        nout = NCOMP[quantity]
         if out is None:
             out = self.empty((nout, nx, len(ax[1]), len(ax[2])), torch.float32)
         idx = self.empty((nx, len(ax[1]), len(ax[2])), torch.int32) if want_index else None
@@ -432,6 +505,7 @@ class HipKernels:
     def field_algebra(self, chans, quantity, flags, Lcell):
         self._stream()
         ncell = chans[0].numel()
+        quantity = self._set_weight(quantity)
         self._chk(self.lib.vps_field_algebra(self.ctx, quantity, flags, float(Lcell),
                                              self._ptr(chans, torch.float32), ncell))
 
@@ -439,7 +513,8 @@ class HipKernels:
         """Fields of `quantity` from the four channels, which are left untouched: -> [3 | 1 | 4, ...] float32."""
         self._stream()
         ncell = chans[0].numel()
-        nout = 1 if quantity == ENERGY else (4 if quantity == VM else 3)
+        quantity = self._set_weight(quantity)
+        nout = NCOMP[quantity]
         out = self.empty((nout,) + tuple(chans.shape[1:]), torch.float32)
         self._chk(self.lib.vps_field_algebra_out(self.ctx, quantity, flags, float(Lcell),
                                                  self._ptr(chans, torch.float32), ncell, self._ptr(out)))
@@ -538,11 +613,13 @@ class HipKernels:
 
     def deposit_fft_z(self, pos, vel, rho, N, Lbox, x0, nx, quantity, flags=0, zimg=None, reuse_sort=None, slab_particles=None,
                       component=None):
-        """Fused deposit + field algebra + z pass -> z images [ncomp, zimage_elems] (ncomp = 1 for ENERGY, else 3).
+        """Fused deposit + field algebra + z pass -> z images [ncomp, zimage_elems] (ncomp = 1 for ENERGY, else 3;
+        a WeightedVelocity is a three-component quantity like VELOCITY).
         slab_particles: a bound on the particles inside the slab (count_in_slab): the sort workspace is then sized for it,
         not for all of a replicated particle set.  component: as in deposit_fft_zy."""
         self._stream()
-        ncomp = 1 if quantity == ENERGY else 3
+        quantity = self._set_weight(quantity)
+        ncomp = NCOMP[quantity]
         if component is not None:
             mask = self._component_mask(quantity, component)
             flags |= mask << 4
@@ -823,8 +900,9 @@ class FieldComm(SlabComm):
 
     @staticmethod
     def units(quantities):
-        """The scalar fields of a step, in dealing order: (quantity, component) -- component None for the energy field."""
-        return [(q, c) for q in quantities for c in ((None,) if q == "energy" else (0, 1, 2))]
+        """The scalar fields of a step, in dealing order: (quantity, component) -- component None for the energy field.
+        A quantity is a name or a code; every one but the energy (a WeightedVelocity included) is dealt out by component."""
+        return [(q, c) for q in quantities for c in ((None,) if q in ("energy", ENERGY) else (0, 1, 2))]
 
     def mine(self, quantities):
         """This rank's fields: CONTIGUOUS blocks of the dealing order (the first n mod W ranks take one more), so that a rank's

@@ -369,12 +369,22 @@ class BoxField:
         if quantity == "energy":
             work = k.field_algebra_out(ch, _dev.ENERGY, flags, self.Lcell)
             return [work[0]]
+        if isinstance(quantity, _dev.WeightedVelocity):
+            # w_c = v_c (mass / Lcell^3)^alpha, 0 where the cell is empty (vps_field_algebra_out, gridded input)
+            work = k.field_algebra_out(ch, quantity, flags, self.Lcell)
+            return [work[0], work[1], work[2]]
         raise Exception("""Unrecognized physical quantity name.
-        Supported: 'velocity', 'momentum', 'energy'.""")
+        Supported: 'velocity', 'momentum', 'energy', 'weighted_velocity' (with density_weight=alpha), 'rho13_velocity',
+        'rho12_velocity'.""")
 
     def _power(self, quantity):
         k = _kernels()
         return _expand_half_power(k.power_grid(self._fields(k, quantity), self.Nsize), self.Lbox, self.Nsize)
+
+    def weighted_velocity_power(self, alpha) -> np.ndarray:
+        """(N,N,N) float64 P = 0.5*sum_c |a F w_c|^2 of the density-weighted velocity w = rho^alpha v, rho = get_density(),
+        w = 0 in empty cells (extension; `velocity_power` is alpha = 0 where every cell holds mass)."""
+        return self._power(_dev.WeightedVelocity(alpha))
 
     def velocity_power(self) -> np.ndarray:
         """(N,N,N) float64 P = 0.5*sum_c |a F v_c|^2 (interp.py:501-518)."""
@@ -389,20 +399,25 @@ class BoxField:
         """P of E = mass*(vx^2+vy^2+vz^2) (interp.py:544-557)."""
         return self._power("energy")
 
-    def spctrm(self, quantity="velocity", kmin=None, kmax=None, kres=None, deconvolve=False) -> PowerSpectrum:
+    def spctrm(self, quantity="velocity", kmin=None, kmax=None, kres=None, deconvolve=False, density_weight=None) -> PowerSpectrum:
         """Binned spectrum, P multiplied by 4 pi k^2 (interp.py:560-595): z/y/x FFT passes
         with |F|^2 and the shell histogram fused into the last pass.  `deconvolve` (extension): divide
         |F(k)|^2 by the window W(k)^2 of the field's mass assignment (`deposit_to_field(N, assignment=...)`;
-        exact for the linearly assigned momentum density, a customary approximation for v = rho v / rho)."""
+        exact for the linearly assigned momentum density, a customary approximation for v = rho v / rho and for
+        rho^alpha v, which are not linear in the assigned density).
+        quantity 'weighted_velocity' with density_weight=alpha (extension): the density-weighted velocity w = rho^alpha v,
+        rho = get_density(), w = 0 in empty cells for every alpha; binned, counted and windowed exactly like 'velocity'.
+        'rho13_velocity' and 'rho12_velocity' are alpha = 1/3 (the scaling variable of supersonic turbulence) and 1/2 (the
+        spectrum that integrates to the kinetic energy density).  alpha is any finite number; density_weight with any other
+        quantity name is a ValueError.  Cell densities that are float32 denormals, or whose power leaves the float32 range,
+        are outside the contract."""
+        quantity, qcode = _dev.resolve_quantity(quantity, density_weight)
         k = _kernels()
         pipe = _dev.PowerPipeline(self.Nsize, self.Lbox, kernels=k, comm=_dev.SlabComm(enabled=False),
                                   flavour="library", kmin=kmin, kmax=kmax, kres=kres,
                                   deconvolve=(getattr(self, "assignment", "ngp") if deconvolve else None))
         src = getattr(self, "_src", None)
-        if quantity not in _dev.QUANTITY:
-            raise Exception("""Unrecognized physical quantity name.
-        Supported: 'velocity', 'momentum', 'energy'.""")
-        if src is not None and k.fused_supported(self.Nsize, _dev.QUANTITY[quantity]):
+        if src is not None and k.fused_supported(self.Nsize, qcode):
             # particle-backed field: particles -> z/y-transformed spectra in one go (no grid in HBM)
             flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
             pipe.prepare()
@@ -410,7 +425,7 @@ class BoxField:
                 # (share_energy: spctrm('momentum') leaves the energy field's z image behind; spctrm('energy') right after it
                 #  then launches no deposit of its own -- vpower/device.py)
                 spec, nyq = k.deposit_fft_zy(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize,
-                                             _dev.QUANTITY[quantity], flags, reuse_sort=getattr(self, "_sort_token", None),
+                                             qcode, flags, reuse_sort=getattr(self, "_sort_token", None),
                                              share_energy=k.share_energy_fits(self.Nsize, self.Nsize))
             self._sort_token = k.fused_token()       # a second quantity of this field skips the particle sort
             tab = pipe.finish(*pipe.accumulate_spectra(spec, nyq))
@@ -423,19 +438,20 @@ class BoxField:
             self._nn_spectra = 1
             flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
             f, _ = k.nn_resample_quantity(nn[0], nn[1], (nn[2], nn[2], nn[2]), 0, self.Nsize, self.Lcell,
-                                          _dev.QUANTITY[quantity], flags)
+                                          qcode, flags)
             return PowerSpectrum(pipe.spectrum([f[i] for i in range(f.shape[0])]))
         if quantity == "momentum":
             # p_c = v_c * mass is formed inside the z pass (two reads per line instead of an algebra pass)
             ch = self._device_chans(k)
             comps = [ch[0], ch[0], ch[0]] if REFERENCE_COMPAT["momentum_bug"] else [ch[0], ch[1], ch[2]]
             return PowerSpectrum(pipe.spectrum(comps, weight=ch[3]))
-        fields = self._fields(k, quantity)
+        fields = self._fields(k, qcode if quantity == "weighted_velocity" else quantity)
         return PowerSpectrum(pipe.spectrum(fields))
 
-    def helmholtz_spctrm(self, quantity="velocity", kmin=None, kmax=None, kres=None, deconvolve=False):
-        """Helmholtz decomposition of the binned spectrum of a VECTOR quantity ('velocity' or 'momentum'; extension, the
-        reference has none): -> (total, compressive, solenoidal), three `PowerSpectrum`s of `spctrm`'s layout -- the same
+    def helmholtz_spctrm(self, quantity="velocity", kmin=None, kmax=None, kres=None, deconvolve=False, density_weight=None):
+        """Helmholtz decomposition of the binned spectrum of a VECTOR quantity ('velocity', 'momentum', or the
+        density-weighted velocity: 'weighted_velocity' with density_weight=alpha, 'rho13_velocity', 'rho12_velocity', as in
+        `spctrm`; extension, the reference has none): -> (total, compressive, solenoidal), three `PowerSpectrum`s of `spctrm`'s layout -- the same
         shells, counts, edges, k range and window deconvolution, P multiplied by 4 pi k^2.  total is what `spctrm(quantity)`
         returns; per mode, with F_c = fftn of component c and k'_i = fftfreq(N) * N on each axis with the Nyquist entry
         (index N/2) set to 0,
@@ -445,9 +461,7 @@ class BoxField:
         solenoidal.  The projection is made in registers by the binning x pass (vps_fft_x_bin_helmholtz): no extra pass
         over the spectrum.  Particle-backed fields go through the fused deposit as `spctrm` does (a second quantity of the
         same field skips the particle sort; momentum leaves the energy field behind for `spctrm('energy')`)."""
-        if quantity not in ("velocity", "momentum"):
-            raise Exception("""Unrecognized physical quantity name.
-        Supported by the Helmholtz decomposition: 'velocity', 'momentum' (vector quantities).""")
+        quantity, qcode = _dev.resolve_quantity(quantity, density_weight, supported=_dev.VECTOR_QUANTITIES)
         k = _kernels()
         pipe = _dev.PowerPipeline(self.Nsize, self.Lbox, kernels=k, comm=_dev.SlabComm(enabled=False),
                                   flavour="library", kmin=kmin, kmax=kmax, kres=kres,
@@ -455,11 +469,11 @@ class BoxField:
         flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
         src = getattr(self, "_src", None)
         nn = getattr(self, "_nn_src", None)
-        if src is not None and k.fused_supported(self.Nsize, _dev.QUANTITY[quantity]):
+        if src is not None and k.fused_supported(self.Nsize, qcode):
             pipe.prepare()
             with k.binning_only():      # the spectra go straight into the binning pass
                 spec, nyq = k.deposit_fft_zy(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize,
-                                             _dev.QUANTITY[quantity], flags, reuse_sort=getattr(self, "_sort_token", None),
+                                             qcode, flags, reuse_sort=getattr(self, "_sort_token", None),
                                              share_energy=k.share_energy_fits(self.Nsize, self.Nsize))
             self._sort_token = k.fused_token()
             tabs = pipe.finish_helmholtz(*pipe.accumulate_spectra_helmholtz(spec, nyq))
@@ -468,14 +482,14 @@ class BoxField:
         elif nn is not None and self._nn_spectra == 0:
             self._nn_spectra = 1        # (as spctrm: the search writes this quantity's fields directly)
             f, _ = k.nn_resample_quantity(nn[0], nn[1], (nn[2], nn[2], nn[2]), 0, self.Nsize, self.Lcell,
-                                          _dev.QUANTITY[quantity], flags)
+                                          qcode, flags)
             tabs = pipe.spectrum_helmholtz([f[i] for i in range(3)])
         elif quantity == "momentum":
             ch = self._device_chans(k)
             comps = [ch[0], ch[0], ch[0]] if REFERENCE_COMPAT["momentum_bug"] else [ch[0], ch[1], ch[2]]
             tabs = pipe.spectrum_helmholtz(comps, weight=ch[3])
         else:
-            tabs = pipe.spectrum_helmholtz(self._fields(k, quantity))
+            tabs = pipe.spectrum_helmholtz(self._fields(k, qcode if quantity == "weighted_velocity" else quantity))
         return tuple(PowerSpectrum(t) for t in tabs)
 
     # -- diagnostics (interp.py:639-666) ----------------------------------------------
