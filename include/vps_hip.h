@@ -75,7 +75,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 8
+#define VPS_ABI_VERSION 9
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -348,6 +348,25 @@ size_t vps_deposit_fft_z_workspace_bytes_slab(int64_t np, int64_t np_slab, int N
 int vps_deposit_fft_z_slab(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* vel_dev,
                            const float* rho_dev, int64_t np, int64_t np_slab, int N, double Lbox, int x0, int nx,
                            int quantity, int flags, void* zimg_dev, void* work_dev);
+/* What the bucket sort of a deposit WOULD do (ABI 9; a pure host-side query like vps_fft_y_chunk_block: nothing is enqueued or
+ * allocated): the bucket geometry and the sort's code path for np particles with C channels on the slab [x0, x0 + nx) of an N^3
+ * grid, under the current options and the context's LDS size.  pencil = 0: the bricks of vps_deposit_ngp / vps_deposit_field
+ * (C = 4); pencil = 1: the pencils of vps_deposit_fft_zy / vps_deposit_fft_z (C = 4 only); np_slab >= 0: the slab-sized
+ * workspace of vps_deposit_fft_z_slab (pencils only), < 0: none.  out[] =
+ *   0 bx, 1 by, 2 bz       cells of one bucket per axis
+ *   3 nbuckets, 4 cells    buckets of the slab, cells per bucket; 5: cells is a power of two (shift instead of divide)
+ *   6 two_level            1: two-level sort, 0: one returning atomic per particle (option sort_atomic, or more buckets than
+ *                          the two-level sort covers)
+ *   7 wide_keys            64-bit keys: nbuckets * cells does not fit 32 bits
+ *   8 gshift, 9 ngroups    level-1 groups of 2^gshift buckets; 10 nchunks: level-1 chunks (table = ngroups * nchunks entries)
+ *   11 staged              level-1 scatter staged in LDS, which takes 12 staged_lds bytes of dynamic LDS (above 64 KiB the
+ *                          kernel's limit is raised first)
+ *   13 recompute           the slab's particles are compacted before the sort (np_slab given and worth it)
+ *   14 cap_in              entries of the key / record arrays.
+ * Tests use it to prove which path a case took. */
+#define VPS_DEPOSIT_PLAN_FIELDS 15
+int vps_deposit_plan(vps_ctx* ctx, int64_t np, int C, int N, int x0, int nx, int pencil, int64_t np_slab,
+                     int64_t out[VPS_DEPOSIT_PLAN_FIELDS]);
 int64_t vps_fft_y_chunk_elems(int N, int nx, int G, int nchunks, int chunk);   /* -1: G, nchunks do not divide */
 int vps_fft_y_packed(vps_ctx* ctx, int N);   /* 1: vps_fft_y packs rows now (binning-only scope with a row cut for N) */
 int64_t vps_fft_y_chunk_block(vps_ctx* ctx, int N, int nx, int G, int nchunks, int chunk, int packed);   /* pure size query (host tables only). -1: bad arguments, -2: G x nchunks does not divide N/2, -3: packed without a row cut (vps_last_error says which) */

@@ -646,10 +646,17 @@ __device__ __forceinline__ void algebra_cell(float a, float b, float c, float rh
     m = rho * vol;
   }
   if (quantity == VPS_MOMENTUM) {
+    if (!(flags & VPS_FLAG_INPUT_IS_VM)) {
+      // p = v m = (rho v) vol: one rounding instead of three, no reciprocal -- what the pencil kernel's momentum launch forms
+      // (exact whenever the cell total and vol are: integer data, L = 1, N a power of two).  Every caller of this epilogue
+      // with [rho v, rho] channels gets it: vps_deposit_field, vps_field_algebra[_out], the NN-resample route.  A cell
+      // without mass stays 0 whatever its rho v channels hold, as with v = (rho v) * 0.
+      vx = a; vy = b; vz = c; m = rho != 0.f ? vol : 0.f;
+    }
     out[0] = vx * m;
     out[1] = ((flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG) ? vx : vy) * m;
     out[2] = ((flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG) ? vx : vz) * m;
-    out[3] = m;
+    out[3] = (flags & VPS_FLAG_INPUT_IS_VM) ? m : rho * vol;
   } else if (quantity == VPS_ENERGY) {
     out[0] = m * ((vx * vx + vy * vy) + vz * vz);
     out[1] = out[2] = 0.f;
@@ -1392,6 +1399,36 @@ int64_t vps_count_in_slab(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, int
   (void)hipFree(d);
   if (e != hipSuccess) return vps_fail(ctx, VPS_ERR_HIP, "vps_count_in_slab: %s", hipGetErrorString(e));
   return (int64_t)h;
+}
+
+int vps_deposit_plan(vps_ctx* ctx, int64_t np, int C, int N, int x0, int nx, int pencil, int64_t np_slab,
+                     int64_t out[VPS_DEPOSIT_PLAN_FIELDS]) {
+  if (!ctx) return VPS_ERR_ARG;
+  if (!out) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_plan: null buffer");
+  int rc = check_deposit_args(ctx, "vps_deposit_plan", np, N, 1.0, x0, nx);
+  if (rc) return rc;
+  if (C != 1 && C != 3 && C != 4) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_plan: C=%d channels (supported: 1,3,4)", C);
+  if (pencil && (C != 4 || N < 16 || !vps_pencil_supported(ctx, N)))
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_plan: pencil buckets carry [rho v, rho] records (C = 4) at an N the fused path supports");
+  if (np_slab >= 0 && !pencil) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_plan: a slab-sized workspace exists for pencil buckets only");
+  const Bricks b = pencil ? make_pencils(N, x0, nx, vps_pencil_tp(N)) : make_bricks(N, x0, nx, C);
+  const DepLayout l = dep_layout(np, C, b, np_slab >= 0 ? np_slab : -1);
+  const SortGeom& g = l.geom;
+  const size_t lds_staged = sort_staged_lds(g, C);
+  out[0] = b.bx; out[1] = b.by; out[2] = b.bz;
+  out[3] = l.nbricks;
+  out[4] = b.cells;
+  out[5] = g.cshift >= 0;
+  out[6] = l.two_level;
+  out[7] = l.wide_keys;
+  out[8] = g.gshift;
+  out[9] = g.ngroups;
+  out[10] = g.nchunks;
+  out[11] = l.two_level && sort_staged() && lds_staged <= ctx->lds_per_cu;   // (sort_into_buckets' rule)
+  out[12] = (int64_t)lds_staged;
+  out[13] = l.recompute;
+  out[14] = l.cap_in;
+  return VPS_OK;
 }
 
 size_t vps_deposit_fft_z_workspace_bytes_slab(int64_t np, int64_t np_slab, int N, int nx) {

@@ -83,6 +83,7 @@ SYMBOLS = (
     ("vps_deposit_fft_z_workspace_bytes_slab", C.c_size_t, (_i64, _i64, C.c_int, C.c_int)),
     ("vps_deposit_fft_z_slab", C.c_int, (_vp, _vp, C.c_int, _vp, _vp, _i64, _i64, C.c_int, C.c_double, C.c_int, C.c_int,
                                          C.c_int, C.c_int, _vp, _vp)),
+    ("vps_deposit_plan", C.c_int, (_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i64, C.POINTER(_i64))),
     ("vps_fft_y_chunk_elems", _i64, (C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)),
     ("vps_fft_y_packed", C.c_int, (_vp, C.c_int)),
     ("vps_fft_y_chunk_block", _i64, (_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)),
@@ -117,7 +118,9 @@ KERNEL_KINDS = {"deposit": K_DEPOSIT, "algebra": K_ALGEBRA, "fft_z": K_FFT_Z, "f
                 "exchange": K_EXCHANGE, "exchange_wait": K_EXCHANGE_WAIT}
 
 
-ABI_VERSION = 8   # include/vps_hip.h: VPS_ABI_VERSION
+DEPOSIT_PLAN_FIELDS = ("bx", "by", "bz", "nbuckets", "cells", "cells_pow2", "two_level", "wide_keys", "gshift", "ngroups", "nchunks",
+                       "staged", "staged_lds", "recompute", "cap_in")   # include/vps_hip.h: vps_deposit_plan
+ABI_VERSION = 9   # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

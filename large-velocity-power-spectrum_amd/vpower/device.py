@@ -611,6 +611,15 @@ class HipKernels:
             self._chk(n)
         return n
 
+    def deposit_plan(self, np_, C_, N, x0, nx, pencil=False, slab_particles=None):
+        """What the bucket sort of a deposit of np_ particles with C_ channels on the slab would do under the current options
+        (vps_deposit_plan; nothing runs): {field: int} over _ffi.DEPOSIT_PLAN_FIELDS.  pencil: the buckets of the fused route
+        (C_ = 4) instead of the bricks of deposit / deposit_field; slab_particles: as in deposit_fft_z."""
+        out = (C.c_int64 * len(_ffi.DEPOSIT_PLAN_FIELDS))()
+        self._chk(self.lib.vps_deposit_plan(self.ctx, int(np_), int(C_), int(N), int(x0), int(nx), 1 if pencil else 0,
+                                            -1 if slab_particles is None else int(slab_particles), out))
+        return dict(zip(_ffi.DEPOSIT_PLAN_FIELDS, (int(v) for v in out)))
+
     def deposit_fft_z(self, pos, vel, rho, N, Lbox, x0, nx, quantity, flags=0, zimg=None, reuse_sort=None, slab_particles=None,
                       component=None):
         """Fused deposit + field algebra + z pass -> z images [ncomp, zimage_elems] (ncomp = 1 for ENERGY, else 3;

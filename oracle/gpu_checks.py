@@ -28,11 +28,59 @@ def shell_counts_exact(device, N, k2_axis, thr):
     return counts[1: nb + 1].cpu().numpy()
 
 
+def ngp_fields_float64(rho, rv, vol, quantities):
+    """float64 fields of the NGP cell totals rho = sum rho_p and rv[c] = sum rho_p v_pc: interp.py:272-273 (v = rho v / rho,
+    m = rho Lcell^3; empty cells 0, the rule of :329-331) + 523-525 (p = v m) + 546 (E = m |v|^2); "mass": m alone.
+    -> {quantity: [component fields]} in the shape of rho."""
+    inv = torch.where(rho > 0, 1.0 / rho, torch.zeros_like(rho))
+    v = [a * inv for a in rv]
+    m = rho * vol
+    out = {}
+    for q in quantities:
+        if q == "velocity":
+            out[q] = v
+        elif q == "momentum":
+            out[q] = [v[c] * m for c in range(3)]
+        elif q == "mass":
+            out[q] = [m]
+        else:
+            out[q] = [m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2])]
+    return out
+
+
+def slab_sums(cells, payloads, N, x0, rows, dtype=torch.int64):
+    """Per payload (a tensor [np]) the scatter-add over the cells [np, 3] that lie in the x-rows [x0, x0 + rows): flat
+    tensors of rows * N * N entries, cell (x, y, z) at ((x - x0) N + y) N + z.  dtype int64 with integer payloads is the EXACT
+    NGP deposit (an integer histogram, interp.py:1013 without rounding); float64 is the reference of real-valued data."""
+    cx = cells[:, 0]
+    sel = torch.nonzero((cx >= x0) & (cx < x0 + rows)).squeeze(1)
+    c = cells[sel].to(torch.int64)
+    flat = ((c[:, 0] - x0) * N + c[:, 1]) * N + c[:, 2]
+    del c
+    n3 = rows * N * N
+    return [torch.zeros(n3, dtype=dtype, device=cells.device).index_add_(0, flat, p[sel].to(dtype)) for p in payloads]
+
+
+def exact_slab_reference(cells, rho, vel, N, x0, rows, payload=None):
+    """int64 cell totals of the rows [x0, x0 + rows): [sum rho, sum rho vx, sum rho vy, sum rho vz] of integer-valued rho, vel
+    -- or, payload [np, C] given, of its C integer columns."""
+    if payload is not None:
+        return slab_sums(cells, [payload[:, c] for c in range(payload.shape[1])], N, x0, rows)
+    r = rho.to(torch.int64)
+    return slab_sums(cells, [r] + [r * vel[:, c].to(torch.int64) for c in range(3)], N, x0, rows)
+
+
+def float64_slab_fields(cells, rho, vel, N, L, x0, rows, quantities):
+    """{quantity: [float64 component fields, flat rows * N * N]} of real-valued particles whose cells are known."""
+    d = rho.double()
+    sums = slab_sums(cells, [d] + [d * vel[:, c].double() for c in range(3)], N, x0, rows, torch.float64)
+    return ngp_fields_float64(sums[0], sums[1:], (L / N) ** 3, quantities)
+
+
 def ngp_moments_float64(dpos, dvel, drho, N, L, quantities, rows=128):
     """Per quantity the float64 sum and sum of squares of every component field of the NGP fields: a restatement of
-    interp.py:1010-1013 (cell = (pos // Lcell) % N, scatter-add of [rho v, rho]) + 272-273 (v = rho v / rho, m = rho Lcell^3;
-    empty cells 0, the rule of :329-331) + 523-525 (p = v m) + 546 (E = m |v|^2), in torch float64, one x-slab of `rows` planes
-    at a time.  -> {quantity: [[sum, sum of squares] per component]}."""
+    interp.py:1010-1013 (cell = (pos // Lcell) % N, scatter-add of [rho v, rho]) + the field rules of ngp_fields_float64, in
+    torch float64, one x-slab of `rows` planes at a time.  -> {quantity: [[sum, sum of squares] per component]}."""
     Lcell = L / N
     vol = Lcell ** 3
     lc = torch.tensor(Lcell, dtype=dpos.dtype, device=dpos.device)
@@ -47,27 +95,105 @@ def ngp_moments_float64(dpos, dvel, drho, N, L, quantities, rows=128):
         d = drho[sel].double()
         n3 = rows * N * N
         rho = torch.zeros(n3, dtype=torch.float64, device=dpos.device).index_add_(0, flat, d)
-        inv = torch.where(rho > 0, 1.0 / rho, torch.zeros_like(rho))
-        v = []
-        for c in range(3):
-            a = torch.zeros(n3, dtype=torch.float64, device=dpos.device).index_add_(0, flat, d * dvel[sel, c].double())
-            v.append(a * inv)
-            del a
-        m = rho * vol
-        del rho, inv, flat, d, sel
+        rv = [torch.zeros(n3, dtype=torch.float64, device=dpos.device).index_add_(0, flat, d * dvel[sel, c].double())
+              for c in range(3)]
+        del flat, d, sel
+        fields = ngp_fields_float64(rho, rv, vol, quantities)
+        del rho, rv
         for q in quantities:
-            if q == "velocity":
-                fs = v
-            elif q == "momentum":
-                fs = [v[c] * m for c in range(3)]
-            else:
-                fs = [m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2])]
-            for c, f in enumerate(fs):
+            for c, f in enumerate(fields[q]):
                 out[q][c][0] += float(f.sum().item())
                 out[q][c][1] += float((f * f).sum().item())
-            del fs
-        del v, m
+        del fields
     return out
+
+
+# --------------------------------------------------------------------------- #
+# Constructed particles: the cell of every particle is known before any position exists
+# --------------------------------------------------------------------------- #
+DISTRIBUTIONS = ("uniform", "clump", "half_empty", "ends")
+CELL_SUM_CAP = 1 << 12      # no cell total |sum rho v_c| may pass it: float32 sums stay exact, z transforms far below 0.25
+CLUMP_PER_CELL = 400        # 400 particles x (rho <= 3) x (|v| <= 3) = 3600: room for ~50 background particles per cell
+ENDS_CELLS = 32             # "ends": 2 x 16 cells (y, z) of the first and of the last bucket
+
+
+def ends_count(n, per_cell=CLUMP_PER_CELL):
+    """Particles the "ends" distribution can hold under CELL_SUM_CAP (2 * ENDS_CELLS cells, per_cell each)."""
+    return min(int(n), 2 * ENDS_CELLS * per_cell)
+
+
+# (N, box length, position dtype) of every leg of tests/test_gpu_gridding_matrix.py; tests/test_gridding_reference_cpu.py checks
+# the constructed cells against the oracle at each of them
+GRIDDING_MATRIX = ((48, 1.0, "float32"), (96, 2.5, "float32"), (250, 2.5, "float32"), (384, 1.0, "float64"),
+                   (500, 1.0, "float32"), (512, 1.0, "float32"), (512, 1.0, "float64"), (768, 2.5, "float64"),
+                   (1024, 1.0, "float64"), (2048, 1.0, "float32"), (4096, 1.0, "float32"))
+
+
+def matrix_geometry(N, dtype=None):
+    """(L, torch dtype) of the matrix's legs at N (the first entry of GRIDDING_MATRIX, or the one with `dtype`)."""
+    for n, L, dt in GRIDDING_MATRIX:
+        if n == N and dtype in (None, dt):
+            return L, getattr(torch, dt)
+    raise KeyError((N, dtype))
+
+
+def constructed_particles(device, n, N, L, dtype=torch.float32, dist="uniform", seed=0, wrap=1.0 / 16, chunk=1 << 24,
+                          per_cell=CLUMP_PER_CELL):
+    """-> (cells int32 [n, 3], pos `dtype` [n, 3], rho float32 [n], vel float32 [n, 3]) on `device`, made a chunk at a time.
+    rho is an integer in 1..3, every vel component one in -3..3.  A position is (cell + offset) Lcell + k L in float64, rounded
+    once to `dtype`, with offset in [0.25, 0.75] per axis: the rounding (|pos| <= 3 L: below 2^-11 cells in float32 at
+    N = 4096) and the float32 quotient pos // fl(Lcell) (below 1e-3 cells off for any N, L) stay far inside the cell, so that
+    (pos // Lcell) % N is `cells` BY CONSTRUCTION (tests/test_gridding_reference_cpu.py checks every particle against the
+    oracle).  k = 0, except for a share `wrap` of the particles: k in {-2, -1, 1, 2}, positions outside [0, L) whose stored
+    cell is the wrapped one.
+    dist: "uniform"; "clump": 30 % of the particles (at most CLUMP_PER_CELL per cell, dealt out evenly) in the 2 x 16 x N
+    cells at x = N/3, y = 16 floor(N/48) -- a handful of pencils / bricks -- over a uniform background; "half_empty": uniform in
+    x < N/2 only; "ends": only the cells x = 0, y < 2, z < 16 and x = N - 1, y >= N - 2, z >= N - 16, dealt out evenly
+    (n <= ends_count(n)).  per_cell: the clump's / the ends' particles per cell (above CLUMP_PER_CELL the cap no longer
+    holds: for checks of the positions alone)."""
+    if dist not in DISTRIBUTIONS:
+        raise ValueError(dist)
+    if dist == "ends" and n > ends_count(n, per_cell):
+        raise ValueError("ends: at most %d particles" % ends_count(n, per_cell))
+    if dist in ("clump", "ends") and N < 48:
+        raise ValueError("N >= 48")
+    cells = torch.empty((n, 3), dtype=torch.int32, device=device)
+    pos = torch.empty((n, 3), dtype=dtype, device=device)
+    rho = torch.empty((n,), dtype=torch.float32, device=device)
+    vel = torch.empty((n, 3), dtype=torch.float32, device=device)
+    ncl = 2 * 16 * N
+    nclump = min(int(0.3 * n), per_cell * ncl) if dist == "clump" else 0
+    cx0, cy0 = N // 3, (N // 48) * 16
+    Lcell = L / N
+    for k, i0 in enumerate(range(0, n, chunk)):
+        i1 = min(n, i0 + chunk)
+        m = i1 - i0
+        g = torch.Generator(device=device)
+        g.manual_seed(1000003 * seed + k)
+        c = torch.randint(0, N, (m, 3), generator=g, device=device, dtype=torch.int64)
+        if dist == "half_empty":
+            c[:, 0] = torch.randint(0, N // 2, (m,), generator=g, device=device, dtype=torch.int64)
+        elif dist == "clump" and i0 < nclump:
+            j = torch.arange(i0, min(i1, nclump), device=device, dtype=torch.int64) % ncl
+            c[: j.numel()] = torch.stack((cx0 + j // (16 * N), cy0 + (j // N) % 16, j % N), dim=1)
+        elif dist == "ends":
+            i = torch.arange(i0, i1, device=device, dtype=torch.int64)
+            j = (i // 2) % ENDS_CELLS
+            last = (i % 2) == 1
+            c = torch.stack((torch.where(last, N - 1, 0), torch.where(last, N - 2, 0) + j // 16,
+                             torch.where(last, N - 16, 0) + j % 16), dim=1)
+        off = 0.25 + 0.5 * torch.rand((m, 3), generator=g, device=device, dtype=torch.float64)
+        shift = torch.zeros((m, 3), dtype=torch.float64, device=device)
+        if wrap > 0:
+            kk = torch.randint(0, 4, (m, 3), generator=g, device=device, dtype=torch.int64)
+            kk = torch.where(kk < 2, kk - 2, kk - 1).double()                 # -2, -1, 1, 2
+            shift = torch.where(torch.rand((m, 1), generator=g, device=device, dtype=torch.float64) < wrap, kk * L, shift)
+        pos[i0:i1] = ((c.double() + off) * Lcell + shift).to(dtype)
+        cells[i0:i1] = c.to(torch.int32)
+        rho[i0:i1] = torch.randint(1, 4, (m,), generator=g, device=device, dtype=torch.int64).float()
+        vel[i0:i1] = torch.randint(-3, 4, (m, 3), generator=g, device=device, dtype=torch.int64).float()
+        del c, off, shift
+    return cells, pos, rho, vel
 
 
 def parseval_targets(moments, N):
