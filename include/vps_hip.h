@@ -75,7 +75,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 9
+#define VPS_ABI_VERSION 10
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -229,6 +229,26 @@ int vps_nn_resample(vps_ctx* ctx, const void* pos_dev, int pos_is_f64,
                     const double* qx_host, int nqx, const double* qy_host, int nqy,
                     const double* qz_host, int nqz, int x0, int nx,
                     float* out_dev, int32_t* nn_idx_dev, void* work_dev);
+/* What the cell list of a search over np particles WOULD look like (ABI 10; a pure host-side query without a context, like
+ * vps_nn_workspace_bytes: the geometry depends on np alone, and on the option nn_build_atomic).  out[] =
+ *   0 M, 1 ncell           cells per axis of the list over the particles' bounding box, M^3
+ *   2 sorted               1: two-level LDS bucket sort; 0: counting sort with one global atomic per particle (fewer than four
+ *                          chunks, more groups than the sort covers, or option nn_build_atomic)
+ *   3 gshift, 4 ngroups    level-1 groups of 2^gshift consecutive cells; 5 nchunks: level-1 chunks of particles
+ *   6 lds_scatter, 7 lds_fine   bytes of dynamic LDS of the level-1 scatter and of the level-2 kernel (above 64 KiB the kernel's
+ *                          limit is raised first); 0 when sorted = 0.
+ * VPS_ERR_ARG: np < 1 or beyond int32 indices, or a null buffer. */
+#define VPS_NN_PLAN_FIELDS 8
+int vps_nn_plan(int64_t np, int pos_is_f64, int64_t nq_slab, int64_t out[VPS_NN_PLAN_FIELDS]);
+/* What the last vps_nn_resample* call of this context ran (ABI 10; host-side, nothing is enqueued).  out[] =
+ *   0 kind    VPS_NN_SEARCH_*: the ring search of non-uniform axes (or option nn_query_centric), the scatter kernel or the column
+ *             kernel of uniform axes; -1: no search yet
+ *   1 tiles   workgroups of that search kernel
+ *   2 radii   1: the column kernel's per-tile radii were precomputed
+ *   3 open    lattice points the scatter / column pass handed to the exact fallback (ring search: 0) -- read back only when the
+ *             option nn_stats or the context's timing was on; -1 otherwise. */
+enum { VPS_NN_SEARCH_RING = 0, VPS_NN_SEARCH_SCATTER = 1, VPS_NN_SEARCH_COLUMN = 2 };
+int vps_nn_last_search(vps_ctx* ctx, int64_t out[4]);
 
 /* The same search with the algebra of GasParticles.ann_interp_to_field (vpower/interp.py:272-273) in its epilogue:
  * rhov_dev [np][4] = density_velocity_vector; out_dev [4][nx][nqy][nqz] = vx, vy, vz (= rho v / rho of the nearest

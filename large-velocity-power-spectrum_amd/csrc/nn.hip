@@ -1790,6 +1790,7 @@ struct NnLayout {
   int M;
   bool sorted;      // cell list by the two-level LDS bucket sort (else: counting sort with global atomics)
   NbGeom nb;
+  size_t lds_h, lds_s, lds_f;   // dynamic LDS of nb_hist_kernel, nb_scatter_kernel, nb_fine_kernel (sorted only, else 0)
 };
 
 NnLayout nn_layout(int64_t np, int /*is_f64*/, int64_t nq_slab) {
@@ -1826,6 +1827,12 @@ NnLayout nn_layout(int64_t np, int /*is_f64*/, int64_t nq_slab) {
       l.sorted = false;
   }
   l.total = off;
+  l.lds_h = l.lds_s = l.lds_f = 0;
+  if (l.sorted) {
+    l.lds_h = sizeof(unsigned) * nb.ngroups;
+    l.lds_s = sizeof(unsigned) * ((size_t)NB_CHUNK * 6 + 2 * nb.ngroups + NB_THREADS / 64);
+    l.lds_f = sizeof(unsigned) * ((1u << nb.gshift) + NB_THREADS / 64);
+  }
   return l;
 }
 
@@ -1895,9 +1902,7 @@ int nn_run(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, int C, 
     unsigned* key1 = reinterpret_cast<unsigned*>(work + l.key1);
     float4* rec1 = reinterpret_cast<float4*>(work + l.rec1);
     unsigned* table = reinterpret_cast<unsigned*>(work + l.table);
-    const size_t lds_h = sizeof(unsigned) * nb.ngroups;
-    const size_t lds_s = sizeof(unsigned) * ((size_t)NB_CHUNK * 6 + 2 * nb.ngroups + NB_THREADS / 64);
-    const size_t lds_f = sizeof(unsigned) * ((1u << nb.gshift) + NB_THREADS / 64);
+    const size_t lds_h = l.lds_h, lds_s = l.lds_s, lds_f = l.lds_f;
     auto ks = nb_scatter_kernel<F>;
     VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
     if (lds_f > 64 * 1024)
@@ -1960,7 +1965,12 @@ int nn_run(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, int C, 
     if (tiles > 0x7fffffffLL) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_nn_resample: too many queries for one launch");
     VPS_HIP_CHECK(ctx, hipMemsetAsync(sp.list_count, 0, sizeof(unsigned), ctx->stream));
     sp.tile_r = nullptr;
-    if (column && tiles <= l.ncell) {   // (the cell counters are dead once the list is built: room for one float per tile)
+    const bool radii = column && tiles <= l.ncell;
+    ctx->nn_last[0] = column ? VPS_NN_SEARCH_COLUMN : VPS_NN_SEARCH_SCATTER;   // vps_nn_last_search
+    ctx->nn_last[1] = tiles;
+    ctx->nn_last[2] = radii ? 1 : 0;
+    ctx->nn_last[3] = -1;
+    if (radii) {   // (the cell counters are dead once the list is built: room for one float per tile)
       float* tr = reinterpret_cast<float*>(count);
       vps_launch_timer tm(ctx, VPS_K_NN_BUILD);
       hipLaunchKernelGGL(nn_tile_radius_kernel, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, ctx->stream, sp, tiles, tr);
@@ -2007,12 +2017,17 @@ int nn_run(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, int C, 
       VPS_HIP_CHECK(ctx, hipMemcpyAsync(&open_pts, sp.list_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
       VPS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
       ctx->nn_open_points = open_pts;
+      ctx->nn_last[3] = open_pts;
       if (vps_option("nn_stats", 0) != 0) fprintf(stderr, "[vps] nn: %u of %lld lattice points left to the exact fallback\n", open_pts, nq_slab);
     }
     return VPS_OK;
   }
   const long long qblocks = (long long)((nx + NN_BX - 1) / NN_BX) * ((nqy + NN_BY - 1) / NN_BY) * ((nqz + NN_BZ - 1) / NN_BZ);
   if (qblocks > 0x7fffffffLL) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_nn_resample: too many queries for one launch");
+  ctx->nn_last[0] = VPS_NN_SEARCH_RING;   // vps_nn_last_search: every point settled by the ring search itself, no fallback
+  ctx->nn_last[1] = qblocks;
+  ctx->nn_last[2] = 0;
+  ctx->nn_last[3] = (ctx->timing || vps_option("nn_stats", 0) != 0) ? 0 : -1;
   {
     vps_launch_timer tm(ctx, VPS_K_NN_QUERY);
 #define VPS_NNQ(CC)                                                                                  \
@@ -2037,6 +2052,27 @@ extern "C" {
 size_t vps_nn_workspace_bytes(int64_t np, int pos_is_f64, int64_t nq_slab) {
   if (np < 1) return 256;
   return nn_layout(np, pos_is_f64, nq_slab).total;
+}
+
+int vps_nn_plan(int64_t np, int pos_is_f64, int64_t nq_slab, int64_t out[VPS_NN_PLAN_FIELDS]) {
+  if (np < 1 || np > 0x7fffffffLL || !out) return VPS_ERR_ARG;
+  const NnLayout l = nn_layout(np, pos_is_f64, nq_slab);
+  out[0] = l.M;
+  out[1] = l.ncell;
+  out[2] = l.sorted ? 1 : 0;
+  out[3] = l.nb.gshift;
+  out[4] = l.nb.ngroups;
+  out[5] = l.nb.nchunks;
+  out[6] = (int64_t)l.lds_s;
+  out[7] = (int64_t)l.lds_f;
+  return VPS_OK;
+}
+
+int vps_nn_last_search(vps_ctx* ctx, int64_t out[4]) {
+  if (!ctx) return VPS_ERR_ARG;
+  if (!out) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_last_search: null buffer");
+  for (int i = 0; i < 4; ++i) out[i] = ctx->nn_last[i];
+  return VPS_OK;
 }
 
 static int nn_resample_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* payload_dev,

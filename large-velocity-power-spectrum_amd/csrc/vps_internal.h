@@ -78,6 +78,7 @@ struct vps_ctx {
   vps_comm* comm = nullptr;      // vps_comm_create
 
   unsigned nn_open_points = 0;   // diagnostics: lattice points the last NN scatter pass left to the exact fallback
+  long long nn_last[4] = {-1, 0, 0, -1};   // vps_nn_last_search: kind, tiles, per-tile radii precomputed, open points (-1: not read)
 
   bool timing = false;
   std::vector<vps_timed_launch> launches;

@@ -57,6 +57,8 @@ SYMBOLS = (
                                      C.c_int, C.c_int, _vp, _vp, _vp)),
     ("vps_density_velocity_vector", C.c_int, (_vp, _vp, _vp, _i64, _vp)),
     ("vps_nn_workspace_bytes", C.c_size_t, (_i64, C.c_int, _i64)),
+    ("vps_nn_plan", C.c_int, (_i64, C.c_int, _i64, C.POINTER(_i64))),
+    ("vps_nn_last_search", C.c_int, (_vp, C.POINTER(_i64))),
     ("vps_nn_resample_field", C.c_int, (_vp, _vp, C.c_int, _vp, _i64, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
                                         C.c_double, _vp, _vp, _vp)),
     ("vps_nn_resample_quantity", C.c_int, (_vp, _vp, C.c_int, _vp, _i64, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
@@ -120,7 +122,10 @@ KERNEL_KINDS = {"deposit": K_DEPOSIT, "algebra": K_ALGEBRA, "fft_z": K_FFT_Z, "f
 
 DEPOSIT_PLAN_FIELDS = ("bx", "by", "bz", "nbuckets", "cells", "cells_pow2", "two_level", "wide_keys", "gshift", "ngroups", "nchunks",
                        "staged", "staged_lds", "recompute", "cap_in")   # include/vps_hip.h: vps_deposit_plan
-ABI_VERSION = 9   # include/vps_hip.h: VPS_ABI_VERSION
+NN_PLAN_FIELDS = ("M", "ncell", "sorted", "gshift", "ngroups", "nchunks", "lds_scatter", "lds_fine")   # include/vps_hip.h: vps_nn_plan
+NN_SEARCH_KINDS = ("ring", "scatter", "column")          # include/vps_hip.h: VPS_NN_SEARCH_*
+NN_LAST_SEARCH_FIELDS = ("kind", "tiles", "radii", "open")   # include/vps_hip.h: vps_nn_last_search
+ABI_VERSION = 10  # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

@@ -467,6 +467,20 @@ class HipKernels:
                                            x0, nx, self._ptr(out), self._ptr(idx), self._ptr(work)))
         return out, idx
 
+    def nn_plan(self, np_, pos_is_f64=False, nq_slab=0):
+        """The cell-list geometry of a search over np_ particles under the current options (nn_plan below; nothing runs)."""
+        return nn_plan(np_, pos_is_f64, nq_slab)
+
+    def nn_last_search(self):
+        """What the last nn_resample* call of this context ran (vps_nn_last_search): {"kind": "ring" | "scatter" | "column" (None:
+        no search yet), "tiles": workgroups of the search kernel, "radii": per-tile radii precomputed, "open": lattice points left
+        to the exact fallback (read back only under the option nn_stats or timing; else -1)}."""
+        out = (C.c_int64 * len(_ffi.NN_LAST_SEARCH_FIELDS))()
+        self._chk(self.lib.vps_nn_last_search(self.ctx, out))
+        d = dict(zip(_ffi.NN_LAST_SEARCH_FIELDS, (int(v) for v in out)))
+        d["kind"] = _ffi.NN_SEARCH_KINDS[d["kind"]] if d["kind"] >= 0 else None
+        return d
+
     def nn_resample_field(self, pos, rhov, axes, x0, nx, Lcell, out=None, want_index=False):
         """Exact-NN resampling of [rho v, rho] with v = rho v / rho, mass = rho Lcell^3 formed in the search's
         epilogue: -> [4, nx, ny, nz] float32 = vx, vy, vz, mass (interp.py:246-277 without a pass over the grid)."""
@@ -806,6 +820,16 @@ class HipKernels:
 
 
 _default_kernels = {}
+
+
+def nn_plan(np_, pos_is_f64=False, nq_slab=0):
+    """{field: int} over _ffi.NN_PLAN_FIELDS: the cell list vps_nn_resample* would build for np_ particles under the current
+    options (vps_nn_plan: host only, no context and no device needed)."""
+    out = (C.c_int64 * len(_ffi.NN_PLAN_FIELDS))()
+    rc = _ffi.lib().vps_nn_plan(int(np_), 1 if pos_is_f64 else 0, int(nq_slab), out)
+    if rc != 0:
+        raise _ffi.VpsError("vps_nn_plan failed (%d): np = %r" % (rc, np_))
+    return dict(zip(_ffi.NN_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def default_kernels(device=None):

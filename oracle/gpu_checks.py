@@ -313,3 +313,253 @@ def separable_shell_sums(device, comps, N, L, k2_axis, thr, kz=None, win=None, n
     psum = psum.view(nb + 2, SUB).sum(dim=1)
     counts = counts.view(nb + 2, SUB).sum(dim=1)
     return psum[1: nb + 1].cpu().numpy(), counts[1: nb + 1].cpu().numpy()
+
+
+# --------------------------------------------------------------------------- #
+# Exact nearest neighbours at any particle count: brute force for a few points, a local search with a proof for a slab
+# --------------------------------------------------------------------------- #
+NN_UNCERTIFIED_CAP = 4096   # lattice points per run that nn_slab_reference may leave to nn_brute_force (asserted by the tests)
+NN_BALL_PARTICLES = 50      # uniform-background particles expected inside the certified radius (nn_search_k)
+
+
+def _axis(a, device):
+    return torch.as_tensor(np.asarray(a, dtype=np.float64).copy(), dtype=torch.float64, device=device)
+
+
+def _dist2(qx, qy, qz, px, py, pz):
+    """((qx-px)^2 + (qy-py)^2) + (qz-pz)^2 in float64, every step an op of its own (orc.exact_nn_lattice's association)."""
+    dx = qx - px
+    dx = dx * dx
+    dy = qy - py
+    dy = dy * dy
+    dx = dx + dy
+    del dy
+    dz = qz - pz
+    dz = dz * dz
+    return dx + dz
+
+
+def nn_brute_force(pos, queries, batch=32, chunk=1 << 21):
+    """Exact nearest particle of every query point (float64 [nq, 3]): the minimum of the squared distance over ALL particles, then
+    the lowest index among those equal to it -- orc.exact_nn_lattice's rule (interp.py:1027-1037), in torch on pos.device.
+    `batch` queries against `chunk` particles at a time (temporaries of batch * chunk float64: half a GB; ones of many GB were
+    several times slower per pair on the device); the chunks ascend, so a later chunk takes over only with a strictly smaller
+    distance and the lowest index keeps every tie.  -> (idx int64 [nq], best float64)."""
+    n = pos.shape[0]
+    q = queries.to(torch.float64)
+    idx = torch.full((q.shape[0],), n, dtype=torch.int64, device=pos.device)
+    best = torch.full((q.shape[0],), float("inf"), dtype=torch.float64, device=pos.device)
+    big = torch.tensor(n, dtype=torch.int64, device=pos.device)
+    for j in range(0, n, chunk):
+        p = pos[j:j + chunk].double()
+        px, py, pz = (p[:, c].contiguous()[None, :] for c in range(3))
+        ar = torch.arange(j, j + p.shape[0], dtype=torch.int64, device=pos.device)[None, :]
+        for i in range(0, q.shape[0], batch):
+            b = q[i:i + batch]
+            d = _dist2(b[:, 0:1], b[:, 1:2], b[:, 2:3], px, py, pz)
+            m = d.amin(dim=1)
+            first = torch.where(d == m[:, None], ar, big).amin(dim=1)
+            less = m < best[i:i + batch]
+            idx[i:i + batch] = torch.where(less, first, idx[i:i + batch])
+            best[i:i + batch] = torch.where(less, m, best[i:i + batch])
+            del d
+    return idx, best
+
+
+def lattice_points(axes, x0, nx, flat):
+    """float64 [n, 3] coordinates of the slab's lattice points `flat` (((ix - x0) ny + iy) nz + iz), GATHERED from the axes."""
+    ax, ay, az = axes
+    ny, nz = ay.numel(), az.numel()
+    return torch.stack((ax[x0 + flat // (ny * nz)], ay[(flat // nz) % ny], az[flat % nz]), dim=1)
+
+
+def _nearest_index(a, p):
+    """Index of the point of the monotonic axis `a` nearest to every p (a point half way goes to either side)."""
+    if a.numel() == 1:
+        return torch.zeros(p.shape, dtype=torch.int64, device=p.device)
+    asc = bool(a[-1] > a[0])
+    s = a if asc else a.flip(0)
+    if not bool((s[1:] > s[:-1]).all()):
+        raise ValueError("lattice axes must be strictly monotonic")
+    j = torch.searchsorted((s[:-1] + s[1:]) * 0.5, p.contiguous())
+    return j if asc else (a.numel() - 1) - j
+
+
+def nn_gap_min(axes):
+    """Smallest distance between neighbouring points over the three axes (axes of one point do not count)."""
+    return min(float((a[1:] - a[:-1]).abs().min()) for a in axes if a.numel() > 1)
+
+
+def nn_search_k(nbar, gap_min, want=NN_BALL_PARTICLES):
+    """Smallest k with nbar (4 pi / 3) ((k + 1/2) gap_min)^3 >= want: the certified radius then holds `want` particles of a
+    uniform background of number density nbar on average -- a point without one inside has probability exp(-want)."""
+    k = 0
+    while nbar * (4 * np.pi / 3) * ((k + 0.5) * gap_min) ** 3 < want:
+        k += 1
+    return k
+
+
+def nn_slab_reference(pos, axes, x0, nx, k, budget=1 << 25):
+    """Exact nearest particle of the lattice points axes[0][x0:x0+nx] x axes[1] x axes[2] (float64 tensors on pos.device,
+    strictly monotonic, any spacing) by a LOCAL search: every particle finds the lattice index nearest to it per axis
+    (searchsorted) and offers its float64 distance (_dist2, axis values gathered) to the (2k+1)^3 lattice points around it;
+    scatter_reduce(amin) keeps the minimum, a second pass the lowest particle index among the distances equal to it.
+    -> (idx int64, best float64, certified bool), flat over the slab; idx = np where no particle reached the point.
+    Proof of `certified`: a lattice point more than k indices from a particle's nearest point on some axis is at least
+    (k + 1/2) gap_min from it on that axis (the particle is no farther than half a gap beyond its nearest point's neighbour, the
+    lattice point k whole gaps farther), so best < ((k + 1/2) gap_min (1 - 1e-6))^2 proves that no particle outside the search
+    wins or ties.  Every other point is for nn_brute_force.  Distances are non-negative, so their int64 bit patterns order
+    as they do: the minimum is taken on those (integer atomics), in three rounds of growing share so that the particles of a
+    clump do not all contend for the same few words."""
+    dev = pos.device
+    ax, ay, az = axes
+    ny, nz = ay.numel(), az.numel()
+    n = pos.shape[0]
+    nq = nx * ny * nz
+    jx = _nearest_index(ax, pos[:, 0].double())
+    near = torch.nonzero((jx >= x0 - k) & (jx < x0 + nx + k)).squeeze(1)
+    jx = jx[near]
+    p = pos[near].double()
+    jy = _nearest_index(ay, p[:, 1])
+    jz = _nearest_index(az, p[:, 2])
+    o = torch.arange(-k, k + 1, dtype=torch.int64, device=dev)
+    oy, oz = (t.reshape(-1) for t in torch.meshgrid(o, o, indexing="ij"))
+    step = max(1, budget // oy.numel())
+    inf_bits = int(np.array(np.inf).view(np.int64))
+    best = torch.full((nq,), inf_bits, dtype=torch.int64, device=dev)
+    idx = torch.full((nq,), n, dtype=torch.int64, device=dev)
+
+    def offers():
+        """(flat lattice point, distance bits, particle) of every offer, a block at a time."""
+        for dx in range(-k, k + 1):
+            ix = jx + dx
+            sel = torch.nonzero((ix >= x0) & (ix < x0 + nx)).squeeze(1)
+            for i in range(0, sel.numel(), step):
+                s = sel[i:i + step]
+                iy = jy[s][:, None] + oy[None, :]
+                iz = jz[s][:, None] + oz[None, :]
+                ok = (iy >= 0) & (iy < ny) & (iz >= 0) & (iz < nz)
+                iy.clamp_(0, ny - 1)
+                iz.clamp_(0, nz - 1)
+                ps = p[s]
+                d = _dist2(ax[ix[s]][:, None], ay[iy], az[iz], ps[:, 0:1], ps[:, 1:2], ps[:, 2:3])
+                flat = ((ix[s] - x0)[:, None] * ny + iy) * nz + iz
+                who = near[s][:, None].expand(-1, oy.numel())
+                yield flat[ok], d[ok].view(torch.int64), who[ok]
+
+    for flat, bits, _ in offers():
+        for stride in (256, 16, 1):
+            f, b = flat[::stride], bits[::stride]
+            keep = b < best[f]
+            best.scatter_reduce_(0, f[keep], b[keep], "amin", include_self=True)
+    for flat, bits, who in offers():
+        eq = bits == best[flat]
+        idx.scatter_reduce_(0, flat[eq], who[eq], "amin", include_self=True)
+    best = best.view(torch.float64)
+    bound = ((k + 0.5) * nn_gap_min(axes) * (1 - 1e-6)) ** 2
+    return idx, best, best < bound
+
+
+def nn_settle(pos, axes, x0, nx, idx, best, certified, cap=NN_UNCERTIFIED_CAP):
+    """Finishes nn_slab_reference in place: every uncertified point -- none is skipped -- gets nn_brute_force's answer.
+    -> number of uncertified points; more than `cap` of them is an error of the test's set-up (AssertionError) raised before
+    anything is brute-forced."""
+    open_ = torch.nonzero(~certified).squeeze(1)
+    assert open_.numel() <= cap, "%d uncertified lattice points (cap %d): k is too small for these particles" % (open_.numel(), cap)
+    if open_.numel():
+        i, b = nn_brute_force(pos, lattice_points(axes, x0, nx, open_))
+        idx[open_] = i
+        best[open_] = b
+    return int(open_.numel())
+
+
+def nn_uniform_axis(N):
+    """N points from half a step inside the unit box to half a step BEYOND it on the high side, step 1 / (N - 1): the shape of
+    the library lattice (orc.lattice_axes_library) with points of its own."""
+    h = 1.0 / (N - 1)
+    return (np.arange(N, dtype=np.float64) + 0.5) * h
+
+
+def nn_jittered_axis(N, seed, amp=0.3):
+    """nn_uniform_axis with every point moved by up to +-amp steps: strictly increasing (gaps >= (1 - 2 amp) steps), not uniform."""
+    h = 1.0 / (N - 1)
+    return nn_uniform_axis(N) + np.random.default_rng(seed).uniform(-amp, amp, N) * h
+
+
+def nn_matrix_particles(device, n, dtype, axes, x0, nx, seed, box_steps=10, ndup=1000, nlattice=8):
+    """-> (pos `dtype` [n, 3] on `device`, nbar) for the slab axes[0][x0:x0+nx] of a lattice over the unit box, from a seeded
+    generator: uniform in [0, 1)^3, then
+      * the first tenth of the particles in a Gaussian clump, sigma = 0.01, centred in the slab (clipped to the box);
+      * an empty box of box_steps lattice steps a side starting at the slab's first row, away from the clump (its particles are
+        moved half the unit box up in y, modulo 1);
+      * the last ndup particles are copies of the first ndup particles (beyond the clump's) whose x lies in the slab: exact ties,
+        which the lower index must win;
+      * nlattice particles exactly on lattice points of the slab (as exactly as `dtype` holds them).
+    nbar: number density of the uniform part, 0.9 n."""
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    ax, ay, az = (_axis(a, device) for a in axes)
+    pos = torch.rand((n, 3), generator=g, device=device, dtype=torch.float64)
+    nclump = n // 10
+    xs = torch.sort(ax[x0:x0 + nx]).values
+    centre = torch.stack(((xs[0] + xs[-1]) * 0.5, ay[ay.numel() // 2], az[az.numel() // 2]))
+    pos[:nclump] = (centre[None, :] + 0.01 * torch.randn((nclump, 3), generator=g, device=device, dtype=torch.float64)).clamp_(0.0, 1.0 - 1e-9)
+    hx, hy, hz = (float((a[-1] - a[0]).abs()) / max(a.numel() - 1, 1) for a in (ax, ay, az))
+    steps = torch.tensor([hx, hy, hz], dtype=torch.float64, device=device)
+    lo = torch.stack((xs[0], torch.sort(ay).values[ay.numel() // 5], torch.sort(az).values[az.numel() // 5])) - 0.25 * steps
+    hi = lo + box_steps * steps
+    inside = ((pos >= lo[None, :]) & (pos < hi[None, :])).all(dim=1)
+    pos[:, 1] = torch.where(inside, torch.remainder(pos[:, 1] + 0.5, 1.0), pos[:, 1])
+    for j in range(min(nlattice, n - nclump - min(ndup, n // 8))):
+        pos[nclump + j] = torch.stack((ax[x0 + (nx // 2 + j) % nx], ay[(3 * ay.numel()) // 4 + j % 3], az[(3 * az.numel()) // 4 - j % 5]))
+    ndup = min(ndup, n // 8)
+    if ndup:
+        src = torch.nonzero((pos[nclump:n - ndup, 0] >= xs[0]) & (pos[nclump:n - ndup, 0] <= xs[-1])).squeeze(1)[:ndup] + nclump
+        pos[n - src.numel():] = pos[src]
+    return pos.to(dtype), 0.9 * n
+
+
+# The legs of tests/test_gpu_nn_matrix.py: the smallest particle counts that reach each cell-list geometry (plan: what
+# vps_nn_plan must say), a lattice over the unit box ("uniform": nn_uniform_axis, "library": orc.lattice_axes_library(1, N),
+# "jittered": nn_jittered_axis), slabs (x0, nx) and the option sets every slab is searched under.
+# tests/test_nn_reference_cpu.py runs every leg's set-up at a scaled-down particle count with the same nbar h^3.
+NN_MATRIX = (
+    dict(name="7e6 whole 192", n=7_000_000, dtype="float32", lattice=("uniform", 192), slabs=((0, 192),),
+         runs=({}, {"nn_column": 0}, {"nn_query_centric": 1}),
+         plan=dict(M=167, gshift=14, ngroups=285, sorted=1, lds_fine=65600)),
+    dict(name="1.4e7 float64 256", n=14_000_000, dtype="float64", lattice=("uniform", 256), slabs=((0, 16), (120, 16), (240, 16)),
+         runs=({},), plan=dict(M=210, gshift=15, ngroups=283, sorted=1, lds_fine=131136)),
+    dict(name="2.7e7 320", n=27_000_000, dtype="float32", lattice=("uniform", 320), slabs=((0, 16), (120, 16), (240, 16), (304, 16)),
+         runs=({},), plan=dict(M=262, gshift=15, ngroups=549, sorted=1, lds_fine=131136)),
+    dict(name="5e7 384", n=50_000_000, dtype="float32", lattice=("uniform", 384), slabs=((0, 16), (184, 16), (368, 16)),
+         runs=({},), plan=dict(M=321, gshift=15, ngroups=1010, sorted=1, lds_fine=131136)),
+    dict(name="5e7 library 1024", n=50_000_000, dtype="float32", lattice=("library", 1024), slabs=((0, 8), (504, 8), (1016, 8)),
+         runs=({}, {"nn_column": 0}), plan=dict(M=321, gshift=15, ngroups=1010, sorted=1, lds_fine=131136)),
+    dict(name="5e7 jittered 384", n=50_000_000, dtype="float32", lattice=("jittered", 384), slabs=((184, 4),),
+         runs=({},), plan=dict(M=321, gshift=15, ngroups=1010, sorted=1, lds_fine=131136)),
+    dict(name="1e8 448", n=100_000_000, dtype="float32", lattice=("uniform", 448), slabs=((0, 8), (216, 8), (440, 8)),
+         runs=({},), plan=dict(M=405, gshift=15, ngroups=2028, sorted=1, lds_fine=131136)),
+    dict(name="1.05e8 448", n=105_000_000, dtype="float32", lattice=("uniform", 448), slabs=((0, 8), (216, 8), (440, 8)),
+         runs=({},), plan=dict(M=412, ngroups=2135, sorted=0, lds_fine=0)),
+)
+
+
+def nn_matrix_axes(lattice, seed=0):
+    """The three float64 numpy axes of a leg's lattice."""
+    kind, N = lattice
+    if kind == "uniform":
+        return [nn_uniform_axis(N)] * 3
+    if kind == "library":
+        from oracle import vps_oracle as orc
+        return [orc.lattice_axes_library(1.0, N)] * 3
+    if kind == "jittered":
+        return [nn_jittered_axis(N, seed + a) for a in range(3)]
+    raise ValueError(kind)
+
+
+def nn_search_kind(lattice, opts):
+    """The search vps_nn_resample must report for a leg's lattice under `opts`: the column kernel wherever the lattice is
+    uniform and about as fine as the particles are dense (every leg here: mean spacing / step <= 2.8 against a cutoff near 3)."""
+    if lattice[0] == "jittered" or opts.get("nn_query_centric"):
+        return "ring"
+    return "scatter" if opts.get("nn_column") == 0 else "column"
