@@ -8,7 +8,7 @@
 //   1. sort    : the particles' records {cell-in-bucket, payload[C]} are grouped by BUCKET (a brick of
 //                bx*by*bz cells whose C float channels fit an LDS tile, or a z-pass pencil on the
 //                fused path) by a two-level LDS bucket sort -- chunk histograms, one scan, LDS-staged
-//                runs, one workgroup per coarse group (see "Two-level bucket sort" below).  No global
+//                runs, one workgroup per coarse group (bucket_sort.h, shared with the NN cell list).  No global
 //                atomic per particle, no random 20-byte writes.  A one-atomic-per-particle ranking
 //                (brick_rank_kernel / brick_scatter_kernel) remains for bucket counts or key ranges
 //                the sort does not cover.
@@ -30,6 +30,7 @@
 
 #include "vps_internal.h"
 #include "scan.h"
+#include "bucket_sort.h"
 
 namespace {
 
@@ -188,77 +189,33 @@ __global__ void __launch_bounds__(256)
   for (int c = 0; c < C; ++c) rec[1 + c] = __float_as_uint(val[c]);
 }
 
-// ------------------------------------------------------------------------------
-// Two-level bucket sort: the same records / start[] as rank -> scan -> scatter above, but
-// without a global atomic per particle (memory-side atomics cap that pass at ~2.4e10
-// particles/s) and without 20-byte random writes.
-//   level 1: chunks of SORT_CHUNK particles; per-chunk LDS histogram over coarse groups of
-//            2^gshift consecutive buckets -> table[group][chunk] -> exclusive scan -> each chunk
-//            ranks its particles in LDS, stages its records in LDS in group order and streams
-//            {key, payload} into its own contiguous run of every group
-//   level 2: one workgroup per group: LDS histogram over the group's buckets, LDS scan
-//            (-> start[]), second sweep places {loc, payload} at its final slot
-// Slots inside one bucket come out in no particular order (as with the atomic ranks).
-// ------------------------------------------------------------------------------
-#ifndef VPS_SORT_THREADS
-#define VPS_SORT_THREADS 1024
-#endif
+// ---- the two-level bucket sort (bucket_sort.h) as the deposit uses it ----------------------------------------------------
+// Records {cell-in-bucket, payload[C]} grouped by bucket + start[], the same as rank -> scan -> scatter above gives, from the
+// shared kernels: two particles per thread in level 1, final records that keep their cell-in-bucket word.
 #ifndef VPS_SORT_ITEMS
 #define VPS_SORT_ITEMS 2
 #endif
-constexpr int SORT_THREADS = VPS_SORT_THREADS;   // level 1: chunk = SORT_THREADS * SORT_ITEMS particles
 constexpr int SORT_ITEMS = VPS_SORT_ITEMS;
 constexpr int SORT_CHUNK = SORT_THREADS * SORT_ITEMS;
-constexpr int FINE_THREADS = 1024;  // level 2: one big workgroup per group
-constexpr unsigned SORT_INVALID = 0xffffffffu;
-// words per level-1 record {key, payload[C]}.  (Padding the 5-word record of C = 4 to an aligned 32-byte sector was
-// measured: the level-1 scatter gains 10 %, level 2 loses 50 % to the extra bytes.)
-__host__ __device__ constexpr int sort_rec1_words(int C) { return C + 1; }
 
-struct SortGeom {
-  int gshift, ngroups;     // buckets per group = 1 << gshift
-  int cshift;              // log2(cells) when cells is a power of two, else -1
-  unsigned cells;
-  long long nbuckets, nchunks;
+// key of particle i: bucket * cells + cell-in-bucket through `locate`, invalid outside the slab
+template <typename F, typename K>
+struct DepKeyOf {
+  const F* __restrict__ pos;
+  F lcell, nsize;
+  Bricks b;
+  __device__ __forceinline__ K operator()(long long i) const {
+    unsigned brick, loc;
+    return locate<F>(pos, i, lcell, nsize, b, brick, loc) ? (K)brick * (unsigned)b.cells + loc : sort_invalid<K>();
+  }
 };
 
-// Keys.  The full key of a particle is bucket * cells + cell-in-bucket: K = unsigned while that fits 32 bits, unsigned long
-// long beyond (C4 on one GPU: 2^19 pencils x 2^14 cells).  It only lives in the keys[] array between the level-1 histogram
-// and the level-1 scatter; the level-1 RECORD carries the key relative to its group's first bucket (< 2^gshift * cells),
-// which is all level 2 -- one workgroup per group -- needs, and always 32 bits.
+// keys that are already there (the compacted slab; the block tails of the compaction are invalid)
 template <typename K>
-__device__ __forceinline__ constexpr K sort_invalid() { return (K)~(K)0; }
-
-template <typename K>
-__device__ __forceinline__ unsigned sort_bucket_of(K key, const SortGeom& g) {
-  return (unsigned)(g.cshift >= 0 ? (key >> g.cshift) : (key / g.cells));
-}
-
-template <typename F, typename K>
-__global__ void __launch_bounds__(SORT_THREADS)
-    sort_hist_kernel(const F* __restrict__ pos, long long np, F lcell, F nsize, Bricks b, SortGeom g,
-                     K* __restrict__ keys, unsigned* __restrict__ table) {
-  extern __shared__ unsigned sort_lds[];
-  for (int i = threadIdx.x; i < g.ngroups; i += SORT_THREADS) sort_lds[i] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * SORT_CHUNK;
-#pragma unroll 4
-  for (int k = 0; k < SORT_ITEMS; ++k) {
-    const long long i = base + (long long)k * SORT_THREADS + threadIdx.x;
-    if (i < np) {
-      unsigned brick, loc;
-      K key = sort_invalid<K>();
-      if (locate<F>(pos, i, lcell, nsize, b, brick, loc)) {
-        key = (K)brick * g.cells + loc;
-        atomicAdd(&sort_lds[brick >> g.gshift], 1u);
-      }
-      keys[i] = key;
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < g.ngroups; i += SORT_THREADS)
-    table[(long long)i * g.nchunks + blockIdx.x] = sort_lds[i];
-}
+struct StoredKeyOf {
+  const K* __restrict__ keys;
+  __device__ __forceinline__ K operator()(long long i) const { return keys[i]; }
+};
 
 // ---- slab compaction ---------------------------------------------------------------------------------------------------
 // A rank that holds a REPLICATED particle set but deposits one x-slab of it (scripts/parallel_optimized.py:272-276 loads the
@@ -379,27 +336,6 @@ __global__ void __launch_bounds__(COMPACT_THREADS)
       if ((long long)(blk_base + at) < cap) ckeys[blk_base + at] = sort_invalid<K>();
 }
 
-// level-1 histogram of keys that are already there (the compacted slab)
-template <typename K>
-__global__ void __launch_bounds__(SORT_THREADS)
-    sort_hist_keys_kernel(const K* __restrict__ keys, long long n, SortGeom g, unsigned* __restrict__ table) {
-  extern __shared__ unsigned sort_lds[];
-  for (int i = threadIdx.x; i < g.ngroups; i += SORT_THREADS) sort_lds[i] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * SORT_CHUNK;
-#pragma unroll 4
-  for (int k = 0; k < SORT_ITEMS; ++k) {
-    const long long i = base + (long long)k * SORT_THREADS + threadIdx.x;
-    if (i < n) {
-      const K key = keys[i];
-      if (key != sort_invalid<K>()) atomicAdd(&sort_lds[sort_bucket_of<K>(key, g) >> g.gshift], 1u);   // (block tails of the compaction)
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < g.ngroups; i += SORT_THREADS)
-    table[(long long)i * g.nchunks + blockIdx.x] = sort_lds[i];
-}
-
 template <int C, bool RHOV>
 __device__ __forceinline__ void load_payload(const float* __restrict__ payload, const float* __restrict__ rho,
                                              long long i, float val[C]) {
@@ -419,211 +355,13 @@ __device__ __forceinline__ void load_payload(const float* __restrict__ payload, 
   }
 }
 
-template <int C, bool RHOV, typename K>
-__global__ void __launch_bounds__(SORT_THREADS)
-    sort_scatter_kernel(const K* __restrict__ keys, const float* __restrict__ payload,
-                        const float* __restrict__ rho, long long np, SortGeom g,
-                        const unsigned* __restrict__ table_start, unsigned* __restrict__ rec1) {
-  extern __shared__ unsigned sort_lds[];
-  for (int i = threadIdx.x; i < g.ngroups; i += SORT_THREADS)
-    sort_lds[i] = table_start[(long long)i * g.nchunks + blockIdx.x];
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * SORT_CHUNK;
-#pragma unroll 4
-  for (int k = 0; k < SORT_ITEMS; ++k) {
-    const long long i = base + (long long)k * SORT_THREADS + threadIdx.x;
-    if (i >= np) continue;
-    const K key = keys[i];
-    if (key == sort_invalid<K>()) continue;
-    float val[C];
-    load_payload<C, RHOV>(payload, rho, i, val);
-    const unsigned grp = sort_bucket_of<K>(key, g) >> g.gshift;
-    const unsigned slot = atomicAdd(&sort_lds[grp], 1u);
-    constexpr int W = sort_rec1_words(C);
-    unsigned w[W];
-    w[0] = (unsigned)(key - (K)((unsigned long long)grp << g.gshift) * g.cells);   // relative to the group's first bucket
-#pragma unroll
-    for (int c = 0; c < C; ++c) w[1 + c] = __float_as_uint(val[c]);
-#pragma unroll
-    for (int c = C + 1; c < W; ++c) w[c] = 0;
-    unsigned* rec = rec1 + (size_t)slot * W;
-    if constexpr (W == 2) {
-      *reinterpret_cast<uint2*>(rec) = make_uint2(w[0], w[1]);
-    } else if constexpr (W == 4) {
-      *reinterpret_cast<uint4*>(rec) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < W; ++c) rec[c] = w[c];
-    }
-  }
-}
-
-// Exclusive scan of the LDS array a[0..n), n <= 4 * NT, in place; returns the total.
-// `scratch` holds NT/64 words.  All NT threads of the workgroup must call it.
-template <int NT>
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned* a, int n, unsigned* scratch) {
-  const int per = (n + NT - 1) / NT;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned v[4], mine = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int idx = tid * per + k;
-    v[k] = (k < per && idx < n) ? a[idx] : 0u;
-    mine += v[k];
-  }
-  unsigned inc = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned up = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += up;
-  }
-  if (lane == 63) scratch[wave] = inc;
-  __syncthreads();
-  unsigned before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const unsigned t = scratch[w];
-    if (w < wave) before += t;
-    total += t;
-  }
-  unsigned run = before + inc - mine;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int idx = tid * per + k;
-    if (k < per && idx < n) {
-      a[idx] = run;
-      run += v[k];
-    }
-  }
-  __syncthreads();
-  return total;
-}
-
-// Level-1 scatter, LDS-staged: the chunk's records are first placed in LDS in group order, then
-// streamed out word by word, so each (chunk, group) run leaves the CU as contiguous stores instead
-// of 64 scattered dwords per instruction.  Consecutive chunks own adjacent runs of every group:
-// they are dealt to the SAME XCD (blockIdx % 8, speed only) so that its L2 can merge the partly
-// written lines at run boundaries.
-template <int C, bool RHOV, typename K>
-__global__ void __launch_bounds__(SORT_THREADS)
-    sort_scatter_staged_kernel(const K* __restrict__ keys, const float* __restrict__ payload,
-                               const float* __restrict__ rho, long long np, SortGeom g,
-                               const unsigned* __restrict__ table_start, unsigned* __restrict__ rec1) {
-  constexpr int W = sort_rec1_words(C);
-  extern __shared__ unsigned sort_lds[];
-  unsigned* gbase = sort_lds;                        // [ngroups] first global slot of this chunk's run
-  unsigned* lstart = gbase + g.ngroups;              // [ngroups] counts, then local exclusive starts
-  unsigned* scratch = lstart + g.ngroups;            // [SORT_THREADS / 64]
-  unsigned* gdest = scratch + SORT_THREADS / 64;     // [SORT_CHUNK] global slot of staged record p
-  unsigned* stage = gdest + SORT_CHUNK;              // [SORT_CHUNK * W]
-  const long long per_xcd = (g.nchunks + 7) / 8;
-  const long long chunk = (long long)(blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (chunk >= g.nchunks) return;
-  for (int i = threadIdx.x; i < g.ngroups; i += SORT_THREADS) {
-    gbase[i] = table_start[(long long)i * g.nchunks + chunk];
-    lstart[i] = 0;
-  }
-  __syncthreads();
-  const long long base = chunk * SORT_CHUNK;
-  K key[SORT_ITEMS];
-  unsigned grp[SORT_ITEMS], rk[SORT_ITEMS];
-  float val[SORT_ITEMS][C];
-#pragma unroll
-  for (int k = 0; k < SORT_ITEMS; ++k) {
-    const long long i = base + (long long)k * SORT_THREADS + threadIdx.x;
-    key[k] = (i < np) ? keys[i] : sort_invalid<K>();
-    if (key[k] != sort_invalid<K>()) load_payload<C, RHOV>(payload, rho, i, val[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < SORT_ITEMS; ++k) {
-    if (key[k] != sort_invalid<K>()) {
-      grp[k] = sort_bucket_of<K>(key[k], g) >> g.gshift;
-      rk[k] = atomicAdd(&lstart[grp[k]], 1u);
-    }
-  }
-  __syncthreads();
-  const unsigned total = block_exclusive_scan<SORT_THREADS>(lstart, g.ngroups, scratch);
-#pragma unroll
-  for (int k = 0; k < SORT_ITEMS; ++k) {
-    if (key[k] != sort_invalid<K>()) {
-      const unsigned p = lstart[grp[k]] + rk[k];
-      gdest[p] = gbase[grp[k]] + rk[k];
-      stage[p * W] = (unsigned)(key[k] - (K)((unsigned long long)grp[k] << g.gshift) * g.cells);   // relative to the group's first bucket
-#pragma unroll
-      for (int c = 0; c < C; ++c) stage[p * W + 1 + c] = __float_as_uint(val[k][c]);
-    }
-  }
-  __syncthreads();
-  for (unsigned t = threadIdx.x; t < total * W; t += SORT_THREADS) {
-    const unsigned rec = t / W, wd = t - rec * W;
-    rec1[(size_t)gdest[rec] * W + wd] = stage[t];
-  }
-}
-
-template <int C>
-__global__ void __launch_bounds__(FINE_THREADS)
-    sort_fine_kernel(const unsigned* __restrict__ rec1, SortGeom g, const unsigned* __restrict__ table_start,
-                     unsigned* __restrict__ start, unsigned* __restrict__ records) {
-  constexpr int W = sort_rec1_words(C);
-  extern __shared__ unsigned sort_lds[];          // [G] counts -> cursors, then scan scratch
-  const int G = 1 << g.gshift;
-  unsigned* cur = sort_lds;
-  unsigned* scratch = sort_lds + G;
-  const int grp = blockIdx.x;
-  const unsigned gs = table_start[(long long)grp * g.nchunks];
-  const unsigned ge = table_start[(long long)(grp + 1) * g.nchunks];   // [ngroups*nchunks] = total
-  for (int i = threadIdx.x; i < G; i += FINE_THREADS) cur[i] = 0;
-  __syncthreads();
-  constexpr int U = 4;   // loads of U strides are issued together: the sweeps are latency bound otherwise
-  // The second sweep reads the level-1 records with streaming loads: they are dead after it, and what
-  // should stay in the caches are the final records it writes (the accumulation kernel reads them next:
-  // pencil kernel -10 %).  The first sweep keeps plain loads so that the second finds the lines.
-  // Streaming hints on the level-1 scatter itself cost 35 %.
-  for (unsigned j0 = gs + threadIdx.x; j0 < ge; j0 += U * FINE_THREADS) {
-    unsigned key[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned j = j0 + u * FINE_THREADS;
-      key[u] = j < ge ? rec1[(size_t)j * W] : SORT_INVALID;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (key[u] != SORT_INVALID) atomicAdd(&cur[sort_bucket_of<unsigned>(key[u], g) & (G - 1)], 1u);   // (keys relative to the group)
-  }
-  __syncthreads();
-  block_exclusive_scan<FINE_THREADS>(cur, G, scratch);
-  for (int f = threadIdx.x; f < G; f += FINE_THREADS) {
-    const unsigned at = gs + cur[f];
-    cur[f] = at;
-    const long long bucket = (long long)grp * G + f;
-    if (bucket < g.nbuckets) start[bucket] = at;
-  }
-  if (grp == g.ngroups - 1 && threadIdx.x == 0) start[g.nbuckets] = ge;
-  __syncthreads();
-  for (unsigned j0 = gs + threadIdx.x; j0 < ge; j0 += U * FINE_THREADS) {
-    unsigned r[U][W];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned j = j0 + u * FINE_THREADS;
-      r[u][0] = SORT_INVALID;
-      if (j < ge) {
-        const unsigned* src = rec1 + (size_t)j * W;
-#pragma unroll
-        for (int c = 0; c < W; ++c) r[u][c] = __builtin_nontemporal_load(&src[c]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (r[u][0] == SORT_INVALID) continue;
-      const unsigned bucket = sort_bucket_of<unsigned>(r[u][0], g);
-      const size_t slot = atomicAdd(&cur[bucket & (G - 1)], 1u);
-      unsigned* dst = records + slot * W;
-      dst[0] = r[u][0] - bucket * g.cells;
-#pragma unroll
-      for (int c = 1; c < W; ++c) dst[c] = r[u][c];
-    }
-  }
-}
+template <int C_, bool RHOV>
+struct DepPayload {
+  static constexpr int C = C_;
+  const float* __restrict__ payload;
+  const float* __restrict__ rho;
+  __device__ __forceinline__ void load(long long i, float val[C_]) const { load_payload<C_, RHOV>(payload, rho, i, val); }
+};
 
 // Epilogue of the brick kernel: what is written for a cell from its C accumulated channels.
 //   EPI_RAW      : the C channels as they are (deposit_to_grid)
@@ -1013,10 +751,6 @@ bool sort_staged() { return vps_option("sort_staged", 1) != 0; }
 // two-level sort does not cover, and as a cross-check in the tests)
 bool sort_force_atomic() { return vps_option("sort_atomic", 0) != 0; }
 
-size_t sort_staged_lds(const SortGeom& g, int C) {
-  return sizeof(unsigned) * (2 * (size_t)g.ngroups + SORT_THREADS / 64 + (size_t)SORT_CHUNK * (1 + sort_rec1_words(C)));
-}
-
 // np_cap >= 0: the caller's bound on the number of particles inside the slab (vps_count_in_slab): the record arrays are sized
 // for it and the key array disappears -- for ranks that hold a replicated particle set but deposit one slab of it
 DepLayout dep_layout(int64_t np, int C, const Bricks& b, int64_t np_cap = -1) {
@@ -1041,7 +775,7 @@ DepLayout dep_layout(int64_t np, int C, const Bricks& b, int64_t np_cap = -1) {
   l.wide_keys = (unsigned long long)l.nbricks * (unsigned long long)b.cells >= 0xffffffffull;
   l.two_level = !sort_force_atomic() && g.gshift <= 12 && l.nbricks < 0x7fffffffLL &&
                 ((unsigned long long)b.cells << g.gshift) < 0xffffffffull;
-  l.recompute = np_cap >= 0 && np_cap < np && l.two_level && sort_staged() && sort_staged_lds(g, C) <= 160 * 1024 && C == 4;
+  l.recompute = np_cap >= 0 && np_cap < np && l.two_level && sort_staged() && sort_staged_lds(g, C, SORT_ITEMS) <= 160 * 1024 && C == 4;
   l.cap = l.recompute ? np_cap : np;
   // compacted arrays: the slab's particles + one partly used block per workgroup of the compaction launch
   {
@@ -1097,9 +831,8 @@ int sort_into_buckets(vps_ctx* ctx, const F* pos, const float* payload, const fl
     unsigned* table_start = reinterpret_cast<unsigned*>(work + l.table_start);
     unsigned* table_tiles = reinterpret_cast<unsigned*>(work + l.table_tiles);
     unsigned* rec1 = reinterpret_cast<unsigned*>(work + l.rec1);
-    const size_t lds1 = sizeof(unsigned) * g.ngroups;
-    const size_t lds2 = sizeof(unsigned) * ((1u << g.gshift) + FINE_THREADS / 64);
-    const size_t lds_staged = sort_staged_lds(g, C);
+    const size_t lds1 = sort_hist_lds(g), lds2 = sort_fine_lds(g);
+    const size_t lds_staged = sort_staged_lds(g, C, SORT_ITEMS);
     const bool staged = sort_staged() && lds_staged <= ctx->lds_per_cu;
     if (l.recompute && !staged) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "slab-sized sort workspace needs the LDS-staged scatter");
     auto level1 = [&](auto* keys) -> int {
@@ -1128,33 +861,34 @@ int sort_into_buckets(vps_ctx* ctx, const F* pos, const float* payload, const fl
             VPS_HIP_CHECK(ctx, hipMemsetAsync(start, 0, sizeof(unsigned) * (l.nbricks + 1), ctx->stream));
             return 1;     // (nothing to sort: start[] is all zero)
           }
-          hipLaunchKernelGGL((sort_hist_keys_kernel<K>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
-                             (const K*)keys, n_sort, g, table);
+          hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, StoredKeyOf<K>>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1,
+                             ctx->stream, StoredKeyOf<K>{keys}, n_sort, g, (K*)nullptr, table);
         } else {
           return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "slab-sized sort workspace: [rho v, rho] records only");
         }
       } else {
-        hipLaunchKernelGGL((sort_hist_kernel<F, K>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream, pos,
-                           (long long)np, lcell, nsz, b, g, keys, table);
+        hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, DepKeyOf<F, K>>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1,
+                           ctx->stream, DepKeyOf<F, K>{pos, lcell, nsz, b}, (long long)np, g, keys, table);
       }
       launch_exclusive_scan(ctx->stream, table, (long long)g.ngroups * g.nchunks, table_tiles, table_start);
       if (staged) {
         const unsigned grid = (unsigned)(8 * ((g.nchunks + 7) / 8));
-        auto go = [&](auto kern) -> int {
+        auto go = [&](auto src) -> int {      // src: where the payload comes from
+          auto kern = sort_scatter_staged_kernel<SORT_ITEMS, K, decltype(src)>;
           if (lds_staged > 64 * 1024)
             VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_staged));
-          hipLaunchKernelGGL(kern, dim3(grid), dim3(SORT_THREADS), lds_staged, ctx->stream, (const K*)keys, pay, rho,
-                             n_sort, g, table_start, rec1);
+          hipLaunchKernelGGL(kern, dim3(grid), dim3(SORT_THREADS), lds_staged, ctx->stream, (const K*)keys, src, n_sort, g,
+                             table_start, rec1);
           return VPS_OK;
         };
         int rcs;
-        if constexpr (C == 4) rcs = l.recompute ? go(sort_scatter_staged_kernel<4, false, K>) : go(sort_scatter_staged_kernel<C, RHOV, K>);
-        else rcs = go(sort_scatter_staged_kernel<C, RHOV, K>);
+        if constexpr (C == 4) rcs = l.recompute ? go(DepPayload<4, false>{pay, rho}) : go(DepPayload<C, RHOV>{pay, rho});   // (compacted: [rho v, rho] as stored)
+        else rcs = go(DepPayload<C, RHOV>{pay, rho});
         if (rcs) return rcs;
       } else {
-        hipLaunchKernelGGL((sort_scatter_kernel<C, RHOV, K>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1,
-                           ctx->stream, keys, payload, rho, (long long)np, g, table_start, rec1);
+        hipLaunchKernelGGL((sort_scatter_kernel<SORT_ITEMS, K, DepPayload<C, RHOV>>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS),
+                           lds1, ctx->stream, (const K*)keys, DepPayload<C, RHOV>{payload, rho}, (long long)np, g, table_start, rec1);
       }
       return VPS_OK;
     };
@@ -1163,7 +897,7 @@ int sort_into_buckets(vps_ctx* ctx, const F* pos, const float* payload, const fl
                                 : level1(reinterpret_cast<unsigned*>(work + l.keys));
     if (rc1 == 1) return VPS_OK;     // (empty slab)
     if (rc1) return rc1;
-    hipLaunchKernelGGL(sort_fine_kernel<C>, dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1,
+    hipLaunchKernelGGL((sort_fine_kernel<C, true>), dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1,
                        g, table_start, start, records);
   } else {
     unsigned* tiles = reinterpret_cast<unsigned*>(work + l.tiles);
@@ -1414,7 +1148,7 @@ int vps_deposit_plan(vps_ctx* ctx, int64_t np, int C, int N, int x0, int nx, int
   const Bricks b = pencil ? make_pencils(N, x0, nx, vps_pencil_tp(N)) : make_bricks(N, x0, nx, C);
   const DepLayout l = dep_layout(np, C, b, np_slab >= 0 ? np_slab : -1);
   const SortGeom& g = l.geom;
-  const size_t lds_staged = sort_staged_lds(g, C);
+  const size_t lds_staged = sort_staged_lds(g, C, SORT_ITEMS);
   out[0] = b.bx; out[1] = b.by; out[2] = b.bz;
   out[3] = l.nbricks;
   out[4] = b.cells;

@@ -1,5 +1,7 @@
 // Exclusive prefix sum of 32-bit counts (n entries -> n+1 offsets): three small kernels.
-// Shared by the NN cell list (nn.hip) and the brick deposit (deposit.hip).
+// Shared by the NN cell list (nn.hip) and the brick deposit (deposit.hip): the scan of table[group][chunk] between the two
+// level-1 kernels of the bucket sort both build on (bucket_sort.h, the other header they share), and of the counting sorts'
+// bucket counts.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -524,6 +524,9 @@ def nn_matrix_particles(device, n, dtype, axes, x0, nx, seed, box_steps=10, ndup
 # "jittered": nn_jittered_axis), slabs (x0, nx) and the option sets every slab is searched under.
 # tests/test_nn_reference_cpu.py runs every leg's set-up at a scaled-down particle count with the same nbar h^3.
 NN_MATRIX = (
+    # groups of 8192 cells (gshift 13, from 3.2e6 particles on): two rounds of the sort's level-2 counter scan (4096 counters each)
+    dict(name="3.3e6 whole 64", n=3_300_000, dtype="float32", lattice=("uniform", 64), slabs=((0, 64),),
+         runs=({},), plan=dict(M=130, gshift=13, ngroups=269, sorted=1, lds_fine=32832)),
     dict(name="7e6 whole 192", n=7_000_000, dtype="float32", lattice=("uniform", 192), slabs=((0, 192),),
          runs=({}, {"nn_column": 0}, {"nn_query_centric": 1}),
          plan=dict(M=167, gshift=14, ngroups=285, sorted=1, lds_fine=65600)),

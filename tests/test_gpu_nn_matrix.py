@@ -11,7 +11,8 @@ reference's indices, the search kind through K.nn_last_search, and 512 random po
 the reference itself.  Legs:
   a. coverage guard: gshift 14 and 15, more than 512 groups, the largest sorted geometry, the counting sort and C3's own plan are
      in the matrix;
-  b. the legs of chk.NN_MATRIX: 7e6 particles on the whole 192^3 lattice under the default, scatter and ring searches; 1.4e7
+  b. the legs of chk.NN_MATRIX: 3.3e6 particles on a whole 64^3 lattice (groups of 8192 cells: the first geometry whose level-2
+     counter scan takes two rounds); 7e6 particles on the whole 192^3 lattice under the default, scatter and ring searches; 1.4e7
      (float64 positions) ... 1.05e8 particles on slabs at the first, middle and last rows of 256^3 ... 448^3 lattices and of the
      1024^3 library lattice, and 5e7 on a jittered (non-uniform) lattice;
   c. the edges of the switch into the bucket sort (4 chunks of 4096 particles) on a whole 32^3 lattice, against brute force alone;
