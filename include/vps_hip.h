@@ -44,7 +44,9 @@ enum vps_status {
 /* quantities of BoxField.spctrm (interp.py:573-583) */
 enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                     VPS_VM = 3 /* BoxField form: v in channels 0..2, mass in channel 3 */,
-                    VPS_WEIGHTED_VELOCITY = 4 /* ABI 8: w = rho^alpha v, alpha from vps_set_density_weight (below) */ };
+                    VPS_WEIGHTED_VELOCITY = 4 /* ABI 8: w = rho^alpha v, alpha from vps_set_density_weight (below) */,
+                    VPS_DENSITY = 5 /* ABI 11: the scalar s = rho^alpha (alpha = 1: the density itself), see below */,
+                    VPS_LOG_DENSITY = 6 /* ABI 11: the scalar s = ln rho */ };
 /* flags for vps_field_algebra */
 #define VPS_FLAG_REFERENCE_MOMENTUM_BUG 1 /* py=pz=vx*mass as interp.py:523-525 */
 #define VPS_FLAG_INPUT_IS_VM 2             /* channels already hold vx,vy,vz,mass (a BoxField) */
@@ -75,7 +77,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 10
+#define VPS_ABI_VERSION 11
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -111,6 +113,22 @@ int vps_binning_mode(vps_ctx* ctx);
  * VPS_FLAG_SHARE_ENERGY or VPS_FLAG_REFERENCE_MOMENTUM_BUG.  Outside the contract: densities that are float32 denormals or
  * negative, and powers rho^(alpha - 1) (rho^alpha for gridded input) beyond the float32 range. */
 int vps_set_density_weight(vps_ctx* ctx, double alpha);
+
+/* Density and log-density (ABI 11; an extension): two SCALAR quantities, one output channel / spectrum / z image each, of the
+ * rho that VPS_WEIGHTED_VELOCITY calls rho -- the cell's density total (NGP / CIC / TSC), the nearest particle's density
+ * (exact NN), mass / Lcell^3 for a gridded field (VPS_FLAG_INPUT_IS_VM):
+ *   VPS_DENSITY      s = rho^alpha, alpha from vps_set_density_weight; s = 0 where rho = 0 for every alpha.  alpha = 1 is the
+ *                    plain density and takes NO transcendental: the float32 cell total goes into the transform as it is.
+ *                    Otherwise the power is exp2(alpha log2 rho) on the hardware units.
+ *   VPS_LOG_DENSITY  s = ln rho = log2 rho * ln 2, the natural logarithm of rho in the caller's units; s = 0 where rho = 0.
+ *                    A reference density rho0 (s = ln(rho / rho0)) only moves the k = 0 mode, which no shell holds, AS LONG AS
+ *                    NO CELL IS EMPTY; an empty cell enters the field as if it held rho = 1.  With a sparse NGP grid rescale the
+ *                    densities (so that 1 is a sensible floor) or take the NN route, which has no empty cells.
+ * Both are taken by vps_deposit_field, vps_deposit_fft_zy[_supported], vps_deposit_fft_z[_slab], vps_nn_resample_quantity and
+ * vps_field_algebra[_out] (in place: channel 0); VPS_FLAG_REUSE_SORT as for every quantity.  VPS_ERR_ARG, before anything is
+ * enqueued: VPS_DENSITY on a context whose alpha was never set; either code with VPS_FLAG_COMPONENTS, VPS_FLAG_SHARE_ENERGY or
+ * VPS_FLAG_REFERENCE_MOMENTUM_BUG.  Outside the contract, as for the weighted velocity: densities that are float32 denormals
+ * or negative, powers rho^alpha beyond the float32 range. */
 
 /* ---- memory helpers (so the library is usable without torch) ------------ */
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);
@@ -261,7 +279,8 @@ int vps_nn_resample_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, con
 /* ... and with the algebra of BoxField.spctrm's quantity as well (interp.py:501-557): out_dev [ncomp][nx][nqy][nqz] holds what
  * the spectrum of `quantity` transforms -- VPS_VELOCITY: v (3 channels); VPS_MOMENTUM: p = v * mass (3; with
  * VPS_FLAG_REFERENCE_MOMENTUM_BUG py = pz = px, interp.py:523-525); VPS_ENERGY: E = mass |v|^2 (1); VPS_VM: v and mass (4, =
- * vps_nn_resample_field) -- v = rho v / rho and mass = rho Lcell^3 of the nearest particle, rounded as the reference rounds them.
+ * vps_nn_resample_field); VPS_DENSITY / VPS_LOG_DENSITY (ABI 11): rho^alpha / ln rho of the nearest particle's density (1)
+ * -- v = rho v / rho and mass = rho Lcell^3 of the nearest particle, rounded as the reference rounds them.
  * For `ann_interp_to_field(N).spctrm(q)`: no fourth channel is written and the z pass reads one array per component. */
 int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* rhov_dev,
                              int64_t np, const double* qx_host, int nqx, const double* qy_host, int nqy,
@@ -275,8 +294,9 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
  *                 as interp.py:329-331);
  *   VPS_MOMENTUM: chans[0..2] = v * (rho*Lcell^3)            (interp.py:273,523-525);
  *   VPS_ENERGY  : chans[0]    = (rho*Lcell^3)*(vx^2+vy^2+vz^2) (interp.py:546);
- *   VPS_VM      : chans[0..2] = v, chans[3] = rho*Lcell^3   (BoxField, interp.py:272-275).
- * With VPS_FLAG_INPUT_IS_VM the channels are taken as vx,vy,vz,mass instead.        */
+ *   VPS_VM      : chans[0..2] = v, chans[3] = rho*Lcell^3   (BoxField, interp.py:272-275);
+ *   VPS_DENSITY / VPS_LOG_DENSITY (ABI 11): chans[0] = rho^alpha / ln rho, from channel 3 alone (above).
+ * With VPS_FLAG_INPUT_IS_VM the channels are taken as vx,vy,vz,mass instead (the density codes: rho = mass / Lcell^3). */
 int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell,
                       float* chans_dev, int64_t ncell);
 /* Out-of-place form: chans_dev is only read, the result's channels (3: velocity / momentum, 1: energy,

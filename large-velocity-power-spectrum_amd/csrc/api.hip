@@ -398,13 +398,23 @@ int vps_set_window(vps_ctx* ctx, int N, const float* inv_w2_axis_host) {
 int vps_set_density_weight(vps_ctx* ctx, double alpha) {
   VPS_ENTER(ctx);
   if (!std::isfinite(alpha)) return vps_fail(ctx, VPS_ERR_ARG, "vps_set_density_weight: alpha must be finite");
-  ctx->weight_alpha = alpha;   // host state only: read when a VPS_WEIGHTED_VELOCITY call is enqueued
+  ctx->weight_alpha = alpha;   // host state only: read when a VPS_WEIGHTED_VELOCITY / VPS_DENSITY call is enqueued
   return VPS_OK;
 }
 
 }  // extern "C"
 
 int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags) {
+  if (quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY) {
+    const char* name = quantity == VPS_DENSITY ? "VPS_DENSITY" : "VPS_LOG_DENSITY";
+    if (quantity == VPS_DENSITY && !std::isfinite(ctx->weight_alpha))
+      return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_DENSITY without an exponent (vps_set_density_weight)", who);
+    if (flags & VPS_FLAG_COMPONENT_MASK)
+      return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_FLAG_COMPONENTS with the (scalar) %s field", who, name);
+    if (flags & (VPS_FLAG_SHARE_ENERGY | VPS_FLAG_REFERENCE_MOMENTUM_BUG))
+      return vps_fail(ctx, VPS_ERR_ARG, "%s: %s takes neither VPS_FLAG_SHARE_ENERGY nor VPS_FLAG_REFERENCE_MOMENTUM_BUG", who, name);
+    return VPS_OK;
+  }
   if (quantity != VPS_WEIGHTED_VELOCITY) return VPS_OK;
   if (!std::isfinite(ctx->weight_alpha))
     return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_WEIGHTED_VELOCITY without an exponent (vps_set_density_weight)", who);

@@ -425,15 +425,26 @@ __device__ __forceinline__ void weighted_cell(float a, float b, float c, float r
   out[3] = 0.f;
 }
 
+// The scalar density quantities: s = rho^alpha (VPS_DENSITY; alpha = 1 is rho itself, no transcendental) or s = ln rho
+// (VPS_LOG_DENSITY), 0 where rho = 0; exp2(alpha log2 rho) (vps_rho_pow) and log2 rho * ln 2 on the transcendental units, as in
+// the pencil kernel (fft.hip: pencil_rho_scalar).  rho is channel 3 of [rho v, rho], or mass * inv_vol for a gridded field.
+__device__ __forceinline__ float density_cell(float rho, int quantity, float alpha) {
+  if (quantity == VPS_LOG_DENSITY) return rho != 0.f ? __builtin_amdgcn_logf(rho) * 0.693147180559945309f : 0.f;
+  if (alpha == 1.f) return rho;
+  return rho != 0.f ? vps_rho_pow(rho, alpha) : 0.f;
+}
+
 // QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count.
-// QUANT == VPS_WEIGHTED_VELOCITY: `vol` carries alpha instead (the epilogue needs no cell volume: rho is channel 3 itself).
+// QUANT == VPS_WEIGHTED_VELOCITY, VPS_DENSITY: `vol` carries alpha instead (the epilogue needs no cell volume: rho is channel 3
+// itself); VPS_LOG_DENSITY: it is unused.
 template <int C, int EPI, int QUANT>
 __global__ void __launch_bounds__(256)
     brick_accumulate_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start,
                             Bricks b, long long nbricks, int flags, float vol,
                             float* __restrict__ grid) {
   constexpr int quantity = QUANT;
-  constexpr int NOUT = (EPI == EPI_RAW) ? C : (QUANT == VPS_ENERGY ? 1 : (QUANT == VPS_VM ? 4 : 3));
+  constexpr bool SCALAR_RHO = QUANT == VPS_DENSITY || QUANT == VPS_LOG_DENSITY;
+  constexpr int NOUT = (EPI == EPI_RAW) ? C : ((QUANT == VPS_ENERGY || SCALAR_RHO) ? 1 : (QUANT == VPS_VM ? 4 : 3));
   // Persistent workgroups walk the bricks: the streaming stores of one brick stay in flight
   // while the next bucket is being accumulated, and the tile is re-zeroed as it is read.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -505,7 +516,12 @@ __global__ void __launch_bounds__(256)
           *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
           if (inside) {
             float rx[4], ry[4], rz[4], rw[4];
-            if constexpr (QUANT == VPS_WEIGHTED_VELOCITY) {
+            if constexpr (SCALAR_RHO) {
+              rx[0] = density_cell(c3.x, QUANT, vol);
+              ry[0] = density_cell(c3.y, QUANT, vol);
+              rz[0] = density_cell(c3.z, QUANT, vol);
+              rw[0] = density_cell(c3.w, QUANT, vol);
+            } else if constexpr (QUANT == VPS_WEIGHTED_VELOCITY) {
               weighted_cell(c0.x, c1.x, c2.x, c3.x, 0, 1.f, vol, rx);
               weighted_cell(c0.y, c1.y, c2.y, c3.y, 0, 1.f, vol, ry);
               weighted_cell(c0.z, c1.z, c2.z, c3.z, 0, 1.f, vol, rz);
@@ -543,7 +559,9 @@ __global__ void __launch_bounds__(256)
           for (int c = 0; c < C; ++c) grid[c * plane + cell] = v[c];
         } else {
           float r[4];
-          if constexpr (QUANT == VPS_WEIGHTED_VELOCITY)
+          if constexpr (SCALAR_RHO)
+            r[0] = density_cell(v[3], QUANT, vol);
+          else if constexpr (QUANT == VPS_WEIGHTED_VELOCITY)
             weighted_cell(v[0], v[1], v[2], v[3], 0, 1.f, vol, r);
           else
             algebra_cell(v[0], v[1], v[2], v[3], quantity, flags, vol, r);
@@ -609,6 +627,24 @@ __global__ void __launch_bounds__(256)
   *reinterpret_cast<float4*>(dst + i0) = a;
   *reinterpret_cast<float4*>(dst + ncell + i0) = b;
   *reinterpret_cast<float4*>(dst + 2 * ncell + i0) = c;
+}
+
+// The scalar density quantities of a gridded field (vps_field_algebra[_out] with VPS_DENSITY / VPS_LOG_DENSITY): ONE channel,
+// in place (channel 0) or to `out`, from channel 3 alone -- rho itself, or mass * inv_vol with VPS_FLAG_INPUT_IS_VM.
+__global__ void __launch_bounds__(256)
+    field_density_kernel(float* ch, long long ncell, int quantity, int flags, float inv_vol, float alpha, float* out) {
+  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i0 >= ncell) return;
+  float* dst = out ? out : ch;
+  float4 m = *reinterpret_cast<float4*>(ch + 3 * ncell + i0);
+  if (flags & VPS_FLAG_INPUT_IS_VM) {
+    m.x *= inv_vol; m.y *= inv_vol; m.z *= inv_vol; m.w *= inv_vol;
+  }
+  m.x = density_cell(m.x, quantity, alpha);
+  m.y = density_cell(m.y, quantity, alpha);
+  m.z = density_cell(m.z, quantity, alpha);
+  m.w = density_cell(m.w, quantity, alpha);
+  *reinterpret_cast<float4*>(dst + i0) = m;
 }
 
 // [rho vx, rho vy, rho vz, rho] per particle (interp.py:199-213)
@@ -951,6 +987,16 @@ int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const flo
                            ctx->stream, records, start, b, l.nbricks, flags, (float)ctx->weight_alpha, grid);
       }
     }
+    else if (quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY) {
+      if constexpr (EPI == EPI_ALGEBRA) {   // (one channel; the float argument is alpha for VPS_DENSITY)
+        if (quantity == VPS_DENSITY)
+          hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, VPS_DENSITY>), dim3((unsigned)grid_wg), dim3(256), lds,
+                             ctx->stream, records, start, b, l.nbricks, flags, (float)ctx->weight_alpha, grid);
+        else
+          hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, VPS_LOG_DENSITY>), dim3((unsigned)grid_wg), dim3(256), lds,
+                             ctx->stream, records, start, b, l.nbricks, flags, 0.f, grid);
+      }
+    }
     else VPS_BRICK(VPS_VM);
 #undef VPS_BRICK
   }
@@ -1049,7 +1095,7 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   VPS_ENTER(ctx);
   int rc = check_deposit_args(ctx, "vps_deposit_field", np, N, Lbox, x0, nx);
   if (rc) return rc;
-  if (quantity < 0 || quantity > VPS_WEIGHTED_VELOCITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
+  if (quantity < 0 || quantity > VPS_LOG_DENSITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
   if (flags & VPS_FLAG_INPUT_IS_VM) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_INPUT_IS_VM is meaningless here");
   if (!fields_dev || !work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))
@@ -1062,7 +1108,8 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
 
 int vps_deposit_fft_zy_supported(vps_ctx* ctx, int N, int quantity) {
   if (!ctx) return 0;
-  return (quantity == VPS_VELOCITY || quantity == VPS_MOMENTUM || quantity == VPS_ENERGY || quantity == VPS_WEIGHTED_VELOCITY) &&
+  return (quantity == VPS_VELOCITY || quantity == VPS_MOMENTUM || quantity == VPS_ENERGY || quantity == VPS_WEIGHTED_VELOCITY ||
+          quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY) &&
                  vps_pencil_supported(ctx, N) ? 1 : 0;
 }
 
@@ -1204,7 +1251,8 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   const double lc = Lbox / (double)N;
   const int bug = (quantity == VPS_MOMENTUM) && (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG);
   int chan[3] = {0, bug ? 0 : 1, bug ? 0 : 2};
-  int ncomp = 3;
+  const bool scalar_rho = quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY;   // one field from the rho round alone
+  int ncomp = scalar_rho ? 1 : 3;
   const int only = (flags & VPS_FLAG_COMPONENT_MASK) >> 4;   // bit c: component c is wanted (VPS_FLAG_COMPONENTS); 0: all
   int with_energy = 0;    // VPS_FLAG_SHARE_ENERGY: 1 the momentum launch that also makes the energy field, 2 the energy call that uses it
   if (flags & VPS_FLAG_SHARE_ENERGY) {
@@ -1223,10 +1271,15 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   // (the sort's rank array -- one word per particle, dead once the records are in place -- is the kernel's per-record scratch)
   return vps_fft_pencil_zy(ctx, N, nx, reinterpret_cast<const unsigned*>(work + l.records),
                            reinterpret_cast<const unsigned*>(work + l.start), reinterpret_cast<float*>(work + l.ranks), ncomp, chan,
-                           quantity == VPS_MOMENTUM ? 0 : 1, quantity == VPS_ENERGY ? 1 : 0, (float)(lc * lc * lc),
+                           (quantity == VPS_MOMENTUM || scalar_rho) ? 0 : 1, quantity == VPS_ENERGY ? 1 : 0, (float)(lc * lc * lc),
                            spec_dev, nyq_dev, zimg_dev ? zimg_dev : (void*)(work + l.total), with_energy,
                            quantity == VPS_WEIGHTED_VELOCITY ? 1 : 0,
-                           quantity == VPS_WEIGHTED_VELOCITY ? (float)(ctx->weight_alpha - 1.0) : 0.f);
+                           quantity == VPS_WEIGHTED_VELOCITY ? (float)(ctx->weight_alpha - 1.0) : 0.f,
+                           // (alpha = 1, the plain density: no per-cell function at all)
+                           quantity == VPS_LOG_DENSITY ? PENCIL_SCALAR_LOG
+                           : quantity != VPS_DENSITY ? PENCIL_SCALAR_NONE
+                           : (float)ctx->weight_alpha == 1.f ? PENCIL_SCALAR_RHO : PENCIL_SCALAR_POW,
+                           quantity == VPS_DENSITY ? (float)ctx->weight_alpha : 1.f);
 }
 
 int vps_density_velocity_vector(vps_ctx* ctx, const float* vel_dev, const float* rho_dev, int64_t np,
@@ -1281,7 +1334,7 @@ int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell, float
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,
                           int64_t ncell, float* out_dev) {
   VPS_ENTER(ctx);
-  if (quantity < 0 || quantity > VPS_WEIGHTED_VELOCITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (quantity < 0 || quantity > VPS_LOG_DENSITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
   if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;
   if (ncell < 0 || (ncell & 3)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: ncell must be a multiple of 4");
   if (ncell == 0) return VPS_OK;
@@ -1290,7 +1343,11 @@ int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, c
   const unsigned blocks = (unsigned)((nthreads + 255) / 256);
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
-    if (quantity == VPS_WEIGHTED_VELOCITY)
+    if (quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY)
+      hipLaunchKernelGGL(field_density_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
+                         (long long)ncell, quantity, flags, (float)(1.0 / (Lcell * Lcell * Lcell)),
+                         quantity == VPS_DENSITY ? (float)ctx->weight_alpha : 1.f, out_dev);
+    else if (quantity == VPS_WEIGHTED_VELOCITY)
       hipLaunchKernelGGL(field_weighted_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
                          (long long)ncell, flags, (float)(Lcell * Lcell * Lcell), (float)ctx->weight_alpha, out_dev);
     else

@@ -1041,6 +1041,10 @@ struct PencilParams {
   // rho^wexp, wexp = alpha - 1, per record where the velocity form keeps 1 / rho
   int weighted;
   float wexp;
+  // scalar density quantities (VPS_DENSITY, VPS_LOG_DENSITY; the DENSITY instantiation): PENCIL_SCALAR_RHO the cell total as it
+  // is, PENCIL_SCALAR_POW rho^sexp, PENCIL_SCALAR_LOG ln rho
+  int scalar;
+  float sexp;
 };
 
 // The per-record factor of the dividing launches: 1 / rho (v_rcp_f32), or for the density-weighted velocity rho^(alpha - 1) as
@@ -1055,9 +1059,20 @@ __device__ __forceinline__ float pencil_rho_factor(float r, float wexp) {
     return r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
 }
 
+// The per-cell value of the scalar density launches (DENSITY instantiation) from the cell's density total: rho^sexp as
+// exp2(sexp log2 rho) (vps_rho_pow), or ln rho = log2 rho * ln 2, on the same units; 0 in empty cells for both.  (The plain density,
+// PENCIL_SCALAR_RHO, never gets here: the accumulator goes into the transform as it is.)
+__device__ __forceinline__ float pencil_rho_scalar(float r, int mode, float sexp) {
+  const float s = mode == PENCIL_SCALAR_LOG ? __builtin_amdgcn_logf(r) * 0.693147180559945309f : vps_rho_pow(r, sexp);
+  return r != 0.f ? s : 0.f;
+}
+
 // One workgroup per pencil, on the plan's lanes per line; four waves per SIMD (measured at 512^3 / 1024^3 / 2048^3) need <= 128 VGPRs.
-template <int NC, int TP, bool ENERGY = false, bool WEIGHTED = false>
+// DENSITY: ONE field from ONE round -- the accumulated rho, turned per cell into rho^alpha or ln rho by its records (nothing
+// at all for the plain density) -- and one transform, stored as a workgroup's last field.
+template <int NC, int TP, bool ENERGY = false, bool WEIGHTED = false, bool DENSITY = false>
 __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(const PencilParams p) {
+  static_assert(!(DENSITY && (ENERGY || WEIGHTED)), "the scalar density launch is a form of its own");
   typedef PlanInfo<NC> PI;
   constexpr int L = PI::L, RL = PI::RL, NT = TP * L, N = 2 * NC;
   constexpr int ACC = TP * N;                       // floats of one accumulator
@@ -1101,6 +1116,7 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
   unsigned rloc[KR];
   float rval[KR];
   float rrec[KR];   // 1/rho of the record's cell (velocity; WEIGHTED: rho^(alpha-1)) / sum over components of (rho v_c)^2 of its cell (ENERGY)
+                    // / rho^alpha or ln rho of its cell (DENSITY)
   auto fetch = [&](int word) {   // record word 1..3: rho v_c, 4: rho
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
@@ -1113,8 +1129,8 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
     const unsigned j = s + tid + k * NT;
     rloc[k] = (j < e) ? p.records[(size_t)j * 5] : 0xffffffffu;
   }
-  const bool divide = !ENERGY && p.divide;
-  fetch(divide ? 4 : 1 + p.chan[0]);
+  const bool divide = !ENERGY && !DENSITY && p.divide;
+  fetch((DENSITY || divide) ? 4 : 1 + p.chan[0]);
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   constexpr int R0 = PI::R0, NB0 = RL / R0;
   const int x = pencil / p.nby, y0 = (pencil % p.nby) * TP;
@@ -1151,7 +1167,7 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
   // ENERGY: the three rho*v_c rounds add up q_c^2 per record, a FOURTH round accumulates rho and finishes
   // E = vol * sum / rho in the cells that hold records (all others stay 0)
   const bool we = !ENERGY && p.with_energy;     // (uniform) momentum launch that also produces the energy field
-  const int nround = (ENERGY || we) ? p.ncomp + 1 : p.ncomp;
+  const int nround = DENSITY ? 1 : ((ENERGY || we) ? p.ncomp + 1 : p.ncomp);
   for (int c = 0; c < nround; ++c) {
     // opaque copies: keeps the compiler from hoisting ~50 loop-invariant LDS addresses out of the
     // component loop (they cost more registers than they save instructions, and an occupancy step)
@@ -1176,7 +1192,7 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
     }
     __syncthreads();
     const bool rho_round = (ENERGY || we) && c == p.ncomp;
-    const int word = rho_round ? 4 : 1 + p.chan[c < p.ncomp ? c : 0];
+    const int word = (DENSITY || rho_round) ? 4 : 1 + p.chan[c < p.ncomp ? c : 0];
     // velocity: each term is divided by its cell's rho as it is added -- sum_k (q_k / rho) for the reference's
     // (sum_k q_k) / rho: a different rounding of the same value, within the float32 accumulation noise of the sums
 #pragma unroll
@@ -1225,11 +1241,28 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
         __syncthreads();
       }
     }
+    if constexpr (DENSITY) {
+      // the accumulator holds rho.  The plain density is done; else every record forms s(rho) of its cell, and once everybody
+      // has read rho writes it back (records of one cell write the same bits; cells without a record stay 0) -- the way the
+      // energy launch finishes its rho round
+      if (p.scalar != PENCIL_SCALAR_RHO) {
+#pragma unroll
+        for (int k = 0; k < KR; ++k)
+          if (rloc[k] != 0xffffffffu) rrec[k] = pencil_rho_scalar(acc[rloc[k]], p.scalar, p.sexp);
+        for (unsigned j = tail0; j < e; j += NT) p.side[j] = pencil_rho_scalar(acc[p.records[(size_t)j * 5]], p.scalar, p.sexp);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < KR; ++k)
+          if (rloc[k] != 0xffffffffu) acc[rloc[k]] = rrec[k];
+        for (unsigned j = tail0; j < e; j += NT) acc[p.records[(size_t)j * 5]] = p.side[j];
+        __syncthreads();
+      }
+    }
     // stage-0 inputs straight from the accumulator: z[j] = f[2j] + i f[2j+1]
     cf v[RL];
     {
       const float* q = acc + tc * N;
-      const float sc = (ENERGY || divide || rho_round) ? 1.f : p.vol;
+      const float sc = (ENERGY || DENSITY || divide || rho_round) ? 1.f : p.vol;
 #pragma unroll
       for (int m = 0; m < NB0; ++m)
 #pragma unroll
@@ -1246,7 +1279,7 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
 #pragma unroll
     for (int i = 0; i < RL; ++i) buf[tridx<TP>(out_index_l<NC, L>(lc, i), tc)] = v[i];
     __syncthreads();
-    const int oc = ENERGY ? 0 : c;
+    const int oc = (ENERGY || DENSITY) ? 0 : c;
     cf* out = p.out[oc] + (long long)x * NC * N + y0;
     cf* nyq = p.nyq[oc] + (long long)x * N + y0;
     // 8-line pencils (64-byte output segments) leave in 16-byte stores: the epilogue is bound by store ISSUE (half the
@@ -1255,12 +1288,12 @@ __global__ void __launch_bounds__(TP* PlanInfo<NC>::L, 4) pencil_fft_z_kernel(co
     // 35.1 GB written for 34.4 GB of output); streaming stores otherwise.  Measured at C4: DESIGN.md section 7.
     constexpr bool ST16 = TP == 8 && (NC & 1) == 0 && ((NC / 2) * (TP / 2)) % NT == 0;
     if constexpr (ST16) {
-      if (ENERGY || rho_round)
+      if (ENERGY || DENSITY || rho_round)
         r2c_store_tile16<NC, TP, NT, true>(buf, tidc, p.tw_r2c, out, N, nyq);
       else
         r2c_store_tile16<NC, TP, NT, false>(buf, tidc, p.tw_r2c, out, N, nyq);
     } else
-      r2c_store_tile<NC, TP, NT, false, ENERGY && TP < 16>(buf, tidc, p.tw_r2c, out, N, nyq, TP);
+      r2c_store_tile<NC, TP, NT, false, (ENERGY || DENSITY) && TP < 16>(buf, tidc, p.tw_r2c, out, N, nyq, TP);
   }
 }
 
@@ -1637,7 +1670,9 @@ int launch_pencil(vps_ctx* ctx, const PencilParams& p, long long npencils) {
   constexpr int PENCIL_TP = pencil_tp<NC>();
   if (lds > ctx->lds_per_cu) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "pencil kernel needs %zu B LDS", lds);
   auto kern = p.energy ? pencil_fft_z_kernel<NC, PENCIL_TP, true>
-                       : (p.weighted ? pencil_fft_z_kernel<NC, PENCIL_TP, false, true> : pencil_fft_z_kernel<NC, PENCIL_TP, false>);
+                       : (p.weighted ? pencil_fft_z_kernel<NC, PENCIL_TP, false, true>
+                                     : (p.scalar ? pencil_fft_z_kernel<NC, PENCIL_TP, false, false, true>
+                                                 : pencil_fft_z_kernel<NC, PENCIL_TP, false>));
   if (lds > 64 * 1024)
     VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2946,7 +2981,9 @@ bool vps_pencil_supported(vps_ctx* ctx, int N) {
 // z images [component][B | BN] stay in bwork_dev)
 int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, const unsigned* start, float* side,
                       int ncomp, const int* chan, int divide, int energy, float vol, void* spec_dev, void* nyq_dev,
-                      void* bwork_dev, int with_energy, int weighted, float wexp) {
+                      void* bwork_dev, int with_energy, int weighted, float wexp, int scalar, float sexp) {
+  if (scalar && (ncomp != 1 || divide || energy || with_energy || weighted))
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_pencil_zy: a scalar density quantity is one undivided field of its own");
   if (weighted && (!divide || energy || with_energy))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_pencil_zy: the density-weighted velocity is a dividing vector launch of its own");
   // with_energy = 1: a momentum launch (three components) that leaves the energy field's z image as component 3 of bwork_dev;
@@ -2977,6 +3014,8 @@ int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, cons
   p.with_energy = with_energy == 1;
   p.weighted = weighted;
   p.wexp = wexp;
+  p.scalar = scalar;
+  p.sexp = sexp;
   p.vol = vol;
   p.tw_stage = tz.tw_stage;
   p.tw_r2c = tz.tw_r2c;

@@ -222,17 +222,20 @@ __device__ __forceinline__ float4 srec_load(const float4* __restrict__ srec, uns
 //   NN_ENERGY    E = mass |v|^2 = Lcell^3 |rho v|^2 / rho (interp.py:546): 1 channel
 //   NN_WEIGHTED  w = rho^alpha v = rho v * rho^(alpha - 1) of the nearest particle (VPS_WEIGHTED_VELOCITY; NnEmit::vol carries
 //                alpha - 1: no cell volume enters), the power as exp2((alpha - 1) log2 rho): 3 channels
+//   NN_DENSITY   s = rho^alpha of the nearest particle (VPS_DENSITY; NnEmit::vol carries alpha; alpha = 1: rho as it is, no
+//                transcendental), NN_LOGDENS  s = ln rho = log2 rho * ln 2 (VPS_LOG_DENSITY): 1 channel each, 0 where rho = 0
 // -- the quantity a spectrum needs, formed where the winner is known, so that neither a fourth channel nor a weighted z pass
 // moves bytes for it (C3: momentum -- 12.9 instead of 17.2 GB written, 4.3 GB less read per component in the z pass).
-enum { NN_RAW = 0, NN_VM = 1, NN_VELOCITY = 2, NN_MOMENTUM = 3, NN_MOMBUG = 4, NN_ENERGY = 5, NN_WEIGHTED = 6 };
+enum { NN_RAW = 0, NN_VM = 1, NN_VELOCITY = 2, NN_MOMENTUM = 3, NN_MOMBUG = 4, NN_ENERGY = 5, NN_WEIGHTED = 6, NN_DENSITY = 7,
+       NN_LOGDENS = 8 };
 struct NnEmit {
-  float vol;   // Lcell^3; NN_WEIGHTED: alpha - 1 instead (that form needs no volume).  Not a member of its own: a third word in
+  float vol;   // Lcell^3; NN_WEIGHTED: alpha - 1, NN_DENSITY: alpha instead (those forms need no volume).  Not a member of its own: a third word in
                // this kernel argument costs nn_query_kernel<*, 4> one SGPR and nn_fallback_kernel<*, 4> one more SGPR spill
                // (measured, gfx950), and the existing search kernels are to compile exactly as before
   int form;
 };
 __host__ __device__ inline int nn_form_channels(int form, int C) {
-  return form == NN_RAW ? C : form == NN_VM ? 4 : form == NN_ENERGY ? 1 : 3;
+  return form == NN_RAW ? C : form == NN_VM ? 4 : (form == NN_ENERGY || form == NN_DENSITY || form == NN_LOGDENS) ? 1 : 3;
 }
 // the 1..4 output values of one lattice point from its payload
 __device__ __forceinline__ float4 nn_form_apply(float4 v, NnEmit em) {
@@ -250,6 +253,11 @@ __device__ __forceinline__ float4 nn_form_apply(float4 v, NnEmit em) {
       const float f = v.w != 0.f ? __builtin_amdgcn_exp2f(em.vol * __builtin_amdgcn_logf(v.w)) : 0.f;
       return make_float4(v.x * f, v.y * f, v.z * f, 0.f);
     }
+    case NN_DENSITY: {
+      const float s = v.w != 0.f ? vps_rho_pow(v.w, em.vol) : 0.f;
+      return make_float4(em.vol == 1.f ? v.w : s, 0.f, 0.f, 0.f);
+    }
+    case NN_LOGDENS: return make_float4(v.w != 0.f ? __builtin_amdgcn_logf(v.w) * 0.693147180559945309f : 0.f, 0.f, 0.f, 0.f);
     default: return v;
   }
 }
@@ -1945,9 +1953,14 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
     case VPS_MOMENTUM: form = (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG) ? NN_MOMBUG : NN_MOMENTUM; break;
     case VPS_ENERGY: form = NN_ENERGY; break;
     case VPS_WEIGHTED_VELOCITY: form = NN_WEIGHTED; break;
+    case VPS_DENSITY: form = NN_DENSITY; break;
+    case VPS_LOG_DENSITY: form = NN_LOGDENS; break;
     default: return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: quantity %d", quantity);
   }
   if (int rc = vps_check_weighted(ctx, "vps_nn_resample_quantity", quantity, flags)) return rc;
+  if (form == NN_DENSITY)
+    return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
+                            out_dev, nn_idx_dev, work_dev, NnEmit{(float)ctx->weight_alpha, form});
   if (form == NN_WEIGHTED)
     return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
                             out_dev, nn_idx_dev, work_dev, NnEmit{(float)(ctx->weight_alpha - 1.0), form});

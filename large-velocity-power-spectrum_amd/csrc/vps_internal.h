@@ -90,7 +90,9 @@ int vps_fail(vps_ctx* ctx, int code, const char* fmt, ...);
 double vps_option(const char* name, double dflt);
 
 // VPS_WEIGHTED_VELOCITY needs an exponent on the context and takes neither VPS_FLAG_SHARE_ENERGY nor
-// VPS_FLAG_REFERENCE_MOMENTUM_BUG: VPS_ERR_ARG, checked at the entry points before anything is enqueued (api.hip)
+// VPS_FLAG_REFERENCE_MOMENTUM_BUG: VPS_ERR_ARG, checked at the entry points before anything is enqueued (api.hip).
+// The scalar density quantities go through the same check: VPS_DENSITY needs the exponent too, and VPS_DENSITY /
+// VPS_LOG_DENSITY take none of VPS_FLAG_COMPONENTS, VPS_FLAG_SHARE_ENERGY, VPS_FLAG_REFERENCE_MOMENTUM_BUG.
 int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags);
 
 // Every entry point of the C ABI runs with the context's device current and restores the caller's
@@ -127,6 +129,24 @@ struct vps_launch_timer {
   ~vps_launch_timer();
 };
 
+// The scalar density launches of the pencil kernel (VPS_DENSITY, VPS_LOG_DENSITY): one accumulation round of rho, then the
+// per-cell function of it -- none (alpha = 1: the cell total as it is), rho^sexp, or ln rho.
+// rho^a of the scalar density quantity for rho > 0 (the callers select 0 where rho = 0): exp2(a log2 rho) on the transcendental
+// units (v_log_f32, v_exp_f32) with rho's binary exponent taken out first -- rho = m 2^e, m in [0.5, 1), so
+// a log2 rho = n + (a e - n) + a log2 m with n = rint(a e): the logarithm's result and the argument of exp2 stay of order 1,
+// where one ulp is 6e-8, instead of carrying one ulp of |log2 rho| (1e-6 at 2^13) into the exponent.  A positive field has a
+// mean: a one-sided ulp of the straight form times that mean was 7e-6 of the rms in the thin-slab images.
+#if defined(__HIPCC__)
+__device__ __forceinline__ float vps_rho_pow(float r, float a) {
+  const float e = (float)__builtin_amdgcn_frexp_expf(r);
+  const float n = __builtin_rintf(a * e);
+  const float f = __builtin_fmaf(a, e, -n) + a * __builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(r));
+  return __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
+}
+#endif
+
+enum { PENCIL_SCALAR_NONE = 0, PENCIL_SCALAR_RHO = 1, PENCIL_SCALAR_POW = 2, PENCIL_SCALAR_LOG = 3 };
+
 // fft.hip
 int vps_fft_get_tables(vps_ctx* ctx, int NC, vps_fft_tables* out);
 // most slab ranks G whose segmented x pass (segments of N / G points) exists for lines of N points: 16 for N = 1024, 2048,
@@ -139,7 +159,8 @@ bool vps_pencil_supported(vps_ctx* ctx, int N);
 // side: one float per record (scratch of the kernel: what it keeps per record when a bucket outgrows its registers)
 int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, const unsigned* start, float* side,
                       int ncomp, const int* chan, int divide, int energy, float vol, void* spec_dev, void* nyq_dev,
-                      void* bwork_dev, int with_energy = 0, int weighted = 0, float wexp = 0.f);   // weighted: q * rho^wexp
+                      void* bwork_dev, int with_energy = 0, int weighted = 0, float wexp = 0.f,   // weighted: q * rho^wexp
+                      int scalar = PENCIL_SCALAR_NONE, float sexp = 1.f);
 
 // ---- LDS floating-point accumulation ---------------------------------------------------------
 // gfx950 executes ds_add_f32 far below the LDS rate (measured: about one lane every two clocks per

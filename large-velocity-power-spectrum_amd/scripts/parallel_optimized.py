@@ -45,7 +45,21 @@ def build_parser():
     p.add_argument("--helmholtz", action="store_true",
                    help="Also write the compressive and solenoidal parts of the spectrum (Helmholtz decomposition) to "
                         "Pk_compressive.txt and Pk_solenoidal.txt, in Pk.txt's format.")
+    p.add_argument("--quantity", type=str, default="velocity", metavar="NAME",
+                   help="What to take the spectrum of: velocity (default: the reference's raw nearest-neighbour velocity, Pk.txt "
+                        "unchanged), momentum, energy, weighted_velocity, rho13_velocity, rho12_velocity, density, log_density "
+                        "(vpower.device.resolve_quantity).  Every quantity but velocity needs PartType0/Density in the snapshot.")
+    p.add_argument("--density-weight", type=float, default=None, metavar="ALPHA",
+                   help="Exponent alpha of --quantity weighted_velocity (rho^alpha v) or density (rho^alpha; default 1).")
     return p
+
+
+def resolve_cli_quantity(args):
+    """(name, code) of --quantity / --density-weight through vpower.device.resolve_quantity; --helmholtz keeps refusing scalar
+    quantities.  Raises what resolve_quantity raises."""
+    from vpower import device
+    return device.resolve_quantity(args.quantity, args.density_weight,
+                                   supported=device.VECTOR_QUANTITIES if args.helmholtz else None)
 
 
 def planner(n_total_res, l_total_length, n_box_affordable, n_total_threads):
@@ -103,14 +117,17 @@ def hist_sample(Pk_pair, kmin, kmax, spacing):
     return np.column_stack((centers, P, psum, ns))
 
 
-def load_particles(path):
-    """coords, mass, velocity of PartType0 (parallel_optimized.py:272-276); `.npz` accepted."""
+def load_particles(path, with_density=False):
+    """coords, mass, velocity of PartType0 (parallel_optimized.py:272-276); `.npz` accepted.  with_density: and the particle
+    densities (PartType0/Density; `Density` in an .npz) as a fourth array."""
     if path.endswith(".npz"):
         z = np.load(path)
-        return z["Coordinates"], z["Masses"], z["Velocities"]
+        out = (z["Coordinates"], z["Masses"], z["Velocities"])
+        return out + (z["Density"],) if with_density else out
     import h5py
     with h5py.File(path, "r") as f:
-        return (f["PartType0/Coordinates"][:], f["PartType0/Masses"][:], f["PartType0/Velocities"][:])
+        out = (f["PartType0/Coordinates"][:], f["PartType0/Masses"][:], f["PartType0/Velocities"][:])
+        return out + (f["PartType0/Density"][:],) if with_density else out
 
 
 def _script_table(tab):
@@ -122,11 +139,13 @@ def _script_table(tab):
     return tab
 
 
-def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=None, helmholtz=False):
+def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=None, helmholtz=False, quantity=None, density=None):
     """The body of main() after loading: preprocessing, exact NN at x=i*LCELL (float32
     lattice, :343-346), raw velocity gather (:351), P(k) (:409-463).  Returns the float32
     (nbins,4) table that rank 0 saves; helmholtz=True: the tuple (total, compressive, solenoidal) of such tables
-    (vpower.device.PowerPipeline.accumulate_helmholtz; total is the table of helmholtz=False)."""
+    (vpower.device.PowerPipeline.accumulate_helmholtz; total is the table of helmholtz=False).
+    quantity: a code of vpower.device.resolve_quantity other than plain velocity, with `density` per particle: the fields of
+    that quantity from the nearest particle's [rho v, rho] (vps_nn_resample_quantity) instead of the raw velocity."""
     import torch
     from vpower import device
     k = kernels if kernels is not None else device.default_kernels()
@@ -140,16 +159,23 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
     k.preprocess(pos, vel, k.to_device(np.asarray(mass), torch.float32), True, remove_bulk_velocity)
     # Annoy holds float32 coordinates (add_item, :308): search them as float32
     pos = pos.to(torch.float32)
-    grid, _ = k.nn_resample(pos, vel, (ax, ax, ax), pipe.x0, pipe.nx)
+    if quantity is not None and int(quantity) != device.VELOCITY:
+        if density is None:
+            raise Exception("every quantity but the velocity needs the particle densities")
+        rhov = k.density_velocity_vector(vel, k.to_device(np.asarray(density), torch.float32))
+        grid, _ = k.nn_resample_quantity(pos, rhov, (ax, ax, ax), pipe.x0, pipe.nx, lcell, quantity)
+    else:
+        grid, _ = k.nn_resample(pos, vel, (ax, ax, ax), pipe.x0, pipe.nx)
     if helmholtz:
         tabs = pipe.finish_helmholtz(*pipe.accumulate_helmholtz([grid[0], grid[1], grid[2]]))
         return tuple(_script_table(t) for t in tabs)
-    psum, ns = pipe.accumulate([grid[0], grid[1], grid[2]])
+    psum, ns = pipe.accumulate([grid[i] for i in range(grid.shape[0])])
     return _script_table(pipe.finish(psum, ns))
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    qname, qcode = resolve_cli_quantity(args)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -184,8 +210,13 @@ def main(argv=None):
     if not ok:
         return 0
     print(f"[{datetime.datetime.now()}] Load snapshot: {args.input}", flush=True) if rank == 0 else None
-    coords, mass, velocity = load_particles(args.input)
-    tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot, helmholtz=args.helmholtz)
+    if qname == "velocity":
+        coords, mass, velocity = load_particles(args.input)
+        tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot, helmholtz=args.helmholtz)
+    else:
+        coords, mass, velocity, density = load_particles(args.input, with_density=True)
+        tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot, helmholtz=args.helmholtz, quantity=qcode,
+                                density=density)
     if rank == 0:
         if args.helmholtz:
             tab, comp, sol = tab

@@ -125,7 +125,7 @@ DEPOSIT_PLAN_FIELDS = ("bx", "by", "bz", "nbuckets", "cells", "cells_pow2", "two
 NN_PLAN_FIELDS = ("M", "ncell", "sorted", "gshift", "ngroups", "nchunks", "lds_scatter", "lds_fine")   # include/vps_hip.h: vps_nn_plan
 NN_SEARCH_KINDS = ("ring", "scatter", "column")          # include/vps_hip.h: VPS_NN_SEARCH_*
 NN_LAST_SEARCH_FIELDS = ("kind", "tiles", "radii", "open")   # include/vps_hip.h: vps_nn_last_search
-ABI_VERSION = 10  # include/vps_hip.h: VPS_ABI_VERSION
+ABI_VERSION = 11  # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

@@ -28,13 +28,15 @@ import torch
 
 from . import _ffi
 
-VELOCITY, MOMENTUM, ENERGY, VM, WEIGHTED = 0, 1, 2, 3, 4
-QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED}
+VELOCITY, MOMENTUM, ENERGY, VM, WEIGHTED, DENSITY, LOG_DENSITY = 0, 1, 2, 3, 4, 5, 6
+QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED,
+            "density": DENSITY, "log_density": LOG_DENSITY}
 FLAG_REFERENCE_MOMENTUM_BUG = 1
 FLAG_INPUT_IS_VM = 2
 FLAG_REUSE_SORT = 4
 FLAG_SHARE_ENERGY = 8
-NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3}      # output channels of a quantity
+NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3, DENSITY: 1, LOG_DENSITY: 1}      # output channels of a quantity
+SCALAR_QUANTITIES = ("energy", "density", "log_density")      # one field each: dealt out and transformed as one unit
 
 
 class WeightedVelocity(int):
@@ -67,15 +69,43 @@ class WeightedVelocity(int):
         return "WeightedVelocity(alpha=%r)" % self.alpha
 
 
+class Density(int):
+    """The quantity code of the scalar s = rho^alpha (VPS_DENSITY = 5) TOGETHER with its exponent, built like WeightedVelocity:
+    an int that goes wherever a quantity code goes, compares and hashes by its exponent, and whose `alpha` the kernels wrapper
+    hands to the library right before every call that forms the field.  Density(1.0) is the plain density."""
+
+    def __new__(cls, alpha=1.0):
+        alpha = float(alpha)
+        if not np.isfinite(alpha):
+            raise ValueError("density_weight must be a finite number, got %r" % (alpha,))
+        self = super().__new__(cls, DENSITY)
+        self.alpha = alpha
+        return self
+
+    def __eq__(self, other):
+        return isinstance(other, Density) and self.alpha == other.alpha
+
+    def __ne__(self, other):
+        return not self.__eq__(other)
+
+    def __hash__(self):
+        return hash((DENSITY, self.alpha))
+
+    def __repr__(self):
+        return "Density(alpha=%r)" % self.alpha
+
+
 # names BoxField.spctrm / helmholtz_spctrm take for the density-weighted velocity with a fixed exponent
 WEIGHT_SHORTHANDS = {"rho13_velocity": 1.0 / 3.0, "rho12_velocity": 0.5}
 VECTOR_QUANTITIES = ("velocity", "momentum", "weighted_velocity") + tuple(WEIGHT_SHORTHANDS)
 
 
 def resolve_quantity(quantity, density_weight=None, supported=None):
-    """(name, code) of a quantity name of BoxField.spctrm: name is 'velocity' | 'momentum' | 'energy' | 'weighted_velocity',
-    code the library's (a WeightedVelocity carrying alpha for the last).  'weighted_velocity' needs density_weight = alpha
-    (finite); 'rho13_velocity' / 'rho12_velocity' are alpha = 1/3 and 1/2; density_weight with any other name is an error.
+    """(name, code) of a quantity name of BoxField.spctrm: name is 'velocity' | 'momentum' | 'energy' | 'weighted_velocity' |
+    'density' | 'log_density', code the library's (a WeightedVelocity / Density carrying alpha for those two).
+    'weighted_velocity' needs density_weight = alpha (finite); 'rho13_velocity' / 'rho12_velocity' are alpha = 1/3 and 1/2;
+    'density' is rho^alpha with density_weight = alpha, the plain density (alpha = 1) without; density_weight with any other
+    name is an error.
     `supported` restricts the names (the Helmholtz decomposition: vector quantities)."""
     names = tuple(QUANTITY) + tuple(WEIGHT_SHORTHANDS)
     if supported is not None:
@@ -92,8 +122,10 @@ def resolve_quantity(quantity, density_weight=None, supported=None):
         if density_weight is None:
             raise ValueError("quantity 'weighted_velocity' needs density_weight=alpha (w = rho^alpha v)")
         return quantity, WeightedVelocity(density_weight)
+    if quantity == "density":
+        return quantity, Density(1.0 if density_weight is None else density_weight)
     if density_weight is not None:
-        raise ValueError("density_weight only goes with quantity 'weighted_velocity', not %r" % (quantity,))
+        raise ValueError("density_weight only goes with quantity 'weighted_velocity' or 'density', not %r" % (quantity,))
     return quantity, QUANTITY[quantity]
 
 
@@ -351,10 +383,12 @@ class HipKernels:
 
     def _set_weight(self, quantity):
         """Before a call that forms the fields of `quantity`: a weighted quantity's exponent goes to the context NOW."""
-        if int(quantity) == WEIGHTED:
+        if int(quantity) in (WEIGHTED, DENSITY):
             alpha = getattr(quantity, "alpha", None)
             if alpha is None:
-                raise Exception("the density-weighted velocity needs its exponent: pass device.WeightedVelocity(alpha)")
+                raise Exception("the density-weighted velocity needs its exponent: pass device.WeightedVelocity(alpha)"
+                                if int(quantity) == WEIGHTED else
+                                "the density power rho^alpha needs its exponent: pass device.Density(alpha)")
             self._chk(self.lib.vps_set_density_weight(self.ctx, float(alpha)))
         return int(quantity)
 
@@ -423,7 +457,7 @@ class HipKernels:
     def _component_mask(quantity, component):
         """component: 0..2 or a collection of them -> the bit mask of VPS_FLAG_COMPONENTS."""
         comps = (component,) if isinstance(component, (int, np.integer)) else tuple(component)
-        if quantity == ENERGY or not comps or any(not 0 <= int(c) <= 2 for c in comps) or len(set(comps)) != len(comps):
+        if NCOMP[int(quantity)] == 1 or not comps or any(not 0 <= int(c) <= 2 for c in comps) or len(set(comps)) != len(comps):
             raise Exception("component(s) = distinct values 0..2 of a velocity, momentum or weighted-velocity field")
         mask = 0
         for c in comps:
@@ -933,9 +967,12 @@ class FieldComm(SlabComm):
 
     @staticmethod
     def units(quantities):
-        """The scalar fields of a step, in dealing order: (quantity, component) -- component None for the energy field.
-        A quantity is a name or a code; every one but the energy (a WeightedVelocity included) is dealt out by component."""
-        return [(q, c) for q in quantities for c in ((None,) if q in ("energy", ENERGY) else (0, 1, 2))]
+        """The scalar fields of a step, in dealing order: (quantity, component) -- component None for a scalar quantity (the
+        energy, the density, the log-density: one unit each).  A quantity is a name or a code; every other one (a
+        WeightedVelocity included) is dealt out by component."""
+        def scalar(q):
+            return q in SCALAR_QUANTITIES if isinstance(q, str) else NCOMP[int(q)] == 1
+        return [(q, c) for q in quantities for c in ((None,) if scalar(q) else (0, 1, 2))]
 
     def mine(self, quantities):
         """This rank's fields: CONTIGUOUS blocks of the dealing order (the first n mod W ranks take one more), so that a rank's

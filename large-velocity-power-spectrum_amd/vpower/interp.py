@@ -373,9 +373,13 @@ class BoxField:
             # w_c = v_c (mass / Lcell^3)^alpha, 0 where the cell is empty (vps_field_algebra_out, gridded input)
             work = k.field_algebra_out(ch, quantity, flags, self.Lcell)
             return [work[0], work[1], work[2]]
+        if isinstance(quantity, _dev.Density) or quantity in ("log_density", _dev.LOG_DENSITY):
+            # s = (mass / Lcell^3)^alpha or ln(mass / Lcell^3), 0 where the cell is empty: one channel
+            work = k.field_algebra_out(ch, _dev.LOG_DENSITY if quantity == "log_density" else quantity, flags, self.Lcell)
+            return [work[0]]
         raise Exception("""Unrecognized physical quantity name.
         Supported: 'velocity', 'momentum', 'energy', 'weighted_velocity' (with density_weight=alpha), 'rho13_velocity',
-        'rho12_velocity'.""")
+        'rho12_velocity', 'density' (density_weight=alpha optional), 'log_density'.""")
 
     def _power(self, quantity):
         k = _kernels()
@@ -385,6 +389,16 @@ class BoxField:
         """(N,N,N) float64 P = 0.5*sum_c |a F w_c|^2 of the density-weighted velocity w = rho^alpha v, rho = get_density(),
         w = 0 in empty cells (extension; `velocity_power` is alpha = 0 where every cell holds mass)."""
         return self._power(_dev.WeightedVelocity(alpha))
+
+    def density_power(self, alpha=1.0) -> np.ndarray:
+        """(N,N,N) float64 P = 0.5 |a F s|^2 of the scalar s = rho^alpha, rho = get_density(), s = 0 in empty cells (extension;
+        alpha = 1: the density itself)."""
+        return self._power(_dev.Density(alpha))
+
+    def log_density_power(self) -> np.ndarray:
+        """(N,N,N) float64 P = 0.5 |a F s|^2 of s = ln rho, rho = get_density() in the caller's units; s = 0 in empty cells (they
+        count as rho = 1, see `spctrm`)."""
+        return self._power("log_density")
 
     def velocity_power(self) -> np.ndarray:
         """(N,N,N) float64 P = 0.5*sum_c |a F v_c|^2 (interp.py:501-518)."""
@@ -410,7 +424,12 @@ class BoxField:
         'rho13_velocity' and 'rho12_velocity' are alpha = 1/3 (the scaling variable of supersonic turbulence) and 1/2 (the
         spectrum that integrates to the kinetic energy density).  alpha is any finite number; density_weight with any other
         quantity name is a ValueError.  Cell densities that are float32 denormals, or whose power leaves the float32 range,
-        are outside the contract."""
+        are outside the contract.
+        'density' and 'log_density' (extension): the SCALAR fields s = rho^alpha (density_weight=alpha; without it alpha = 1,
+        the density itself, which takes no transcendental at all) and s = ln rho in the caller's units, on every kind of field;
+        s = 0 in empty cells.  A reference density rho0 in ln(rho / rho0) only moves the k = 0 mode, which no shell holds, as
+        long as no cell is empty; an empty cell counts as rho = 1, so with a sparse NGP grid rescale the densities or use the
+        nearest-neighbour route (`ann_interp_to_field`).  'log_density' takes no density_weight."""
         quantity, qcode = _dev.resolve_quantity(quantity, density_weight)
         k = _kernels()
         pipe = _dev.PowerPipeline(self.Nsize, self.Lbox, kernels=k, comm=_dev.SlabComm(enabled=False),
@@ -445,7 +464,7 @@ class BoxField:
             ch = self._device_chans(k)
             comps = [ch[0], ch[0], ch[0]] if REFERENCE_COMPAT["momentum_bug"] else [ch[0], ch[1], ch[2]]
             return PowerSpectrum(pipe.spectrum(comps, weight=ch[3]))
-        fields = self._fields(k, qcode if quantity == "weighted_velocity" else quantity)
+        fields = self._fields(k, qcode if quantity in ("weighted_velocity", "density") else quantity)
         return PowerSpectrum(pipe.spectrum(fields))
 
     def helmholtz_spctrm(self, quantity="velocity", kmin=None, kmax=None, kres=None, deconvolve=False, density_weight=None):
