@@ -77,7 +77,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 11
+#define VPS_ABI_VERSION 12
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -512,7 +512,11 @@ int vps_pair_k(vps_ctx* ctx, int N, const double* kx_host, const double* ky_host
 /* numpy.histogram(k, bins=edges, weights=w) and the unweighted counts in one pass:
  * edges[i] <= k < edges[i+1], last bin right-closed (interp.py:1474-1477).
  * k_dev, w_dev: float64[n] (w_dev may be NULL: weights 1); edges_host[nbins+1];
- * psum_dev float64[nbins] and nsample_dev uint64[nbins] are accumulated into.  Blocks. */
+ * psum_dev float64[nbins] and nsample_dev uint64[nbins] are accumulated into.  Blocks.
+ * A workgroup keeps the edges and its whole histogram in LDS, 20 nbins + 8 bytes: nbins is admitted up to
+ * vps_hist_max_bins(ctx) (ABI 12) = (LDS bytes a workgroup of the device can have - 8) / 20 -- 8191 with 160 KiB, 3276 with
+ * 64 KiB -- and refused beyond it with VPS_ERR_ARG and a message naming that value, before anything is enqueued. */
+int vps_hist_max_bins(vps_ctx* ctx);
 int vps_hist_pairs(vps_ctx* ctx, const double* k_dev, const double* w_dev, int64_t n,
                    const double* edges_host, int nbins, double* psum_dev,
                    unsigned long long* nsample_dev);

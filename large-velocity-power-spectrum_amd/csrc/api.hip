@@ -118,6 +118,9 @@ int vps_create(vps_ctx** out, int device_id) {
     ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (prop.maxSharedMemoryPerMultiProcessor > 0) ctx->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
   }
+  int per_block = 0;
+  if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id) == hipSuccess && per_block > 0)
+    ctx->lds_per_block = (size_t)per_block;
   strcpy(ctx->err, "no error");
   *out = ctx;
   return VPS_OK;

@@ -658,36 +658,45 @@ __global__ void __launch_bounds__(256)
       make_float4(vel[i * 3 + 0] * r, vel[i * 3 + 1] * r, vel[i * 3 + 2] * r, r);
 }
 
+// Periodic image in [0, N) of an integer-valued cell number held in float64, taken BEFORE the conversion to int: positions far
+// outside the box (1e10, -2.9e8 cells: the NGP route wraps them, cell_of) give cell numbers beyond 2^31, whose conversion is
+// not the number.  Exact below 2^53: c / n is at least 1/n from any integer it does not equal and its rounding error is
+// below that, floor(c / n) n <= |c| and the remainder are exact.  In-range cell numbers come out as they went in.
+__device__ __forceinline__ int wrap_cell(double c, double n) { return (int)(c - floor(c / n) * n); }
+
 // Higher-order mass assignment (cloud-in-cell: 2 cells per axis, triangular-shaped-cloud: 3): every particle becomes
 // S = 8 or 27 weighted sub-particles sitting at the centres of the cells it touches (periodic), which the NGP
 // deposit then adds up -- no new deposit kernel, and with replicated particles no halo exchange between slabs.
 // Not in the reference (it offers NGP interp.py:996, NN :1018 and Voxelize :280); SURVEY.md section 8(f-4).
+// The cell coordinate s = x / Lcell (a division: the correctly rounded quotient, whatever the size of x) and the axis weights
+// are formed in float64 and each weight is rounded to float32 ONCE: a weight is then right to 2^-24 of ITSELF, however small
+// (1 - f next to a cell centre, (1/2 - d)^2 next to a face), where float32 arithmetic on a rounded offset is right to 2^-25
+// of the offset only.  The kernel moves 27 records per particle; the few float64 operations per axis do not show.
 template <typename F>
 __global__ void __launch_bounds__(256)
     assign_expand_kernel(const F* __restrict__ pos, const float* __restrict__ payload, long long np, int C, int N,
-                         double inv_lcell, double lcell, int order, float* __restrict__ pos_out,
-                         float* __restrict__ payload_out) {
+                         double lcell, int order, float* __restrict__ pos_out, float* __restrict__ payload_out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= np) return;
   int c0[3];
   float w[3][3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const double s = (double)pos[i * 3 + a] * inv_lcell;
+    const double s = (double)pos[i * 3 + a] / lcell;
     if (order == 2) {            // CIC: cells floor(s - 1/2) and the next one, weights 1 - f, f
       const double f0 = floor(s - 0.5);
-      const float f = (float)(s - 0.5 - f0);
-      c0[a] = (int)f0;
-      w[a][0] = 1.f - f;
-      w[a][1] = f;
+      const double f = s - 0.5 - f0;
+      c0[a] = wrap_cell(f0, (double)N);
+      w[a][0] = (float)(1.0 - f);
+      w[a][1] = (float)f;
       w[a][2] = 0.f;
     } else {                     // TSC: the cell holding the particle and its two neighbours
       const double ic = floor(s);
-      const float d = (float)(s - (ic + 0.5));
-      c0[a] = (int)ic - 1;
-      w[a][0] = 0.5f * (0.5f - d) * (0.5f - d);
-      w[a][1] = 0.75f - d * d;
-      w[a][2] = 0.5f * (0.5f + d) * (0.5f + d);
+      const double d = s - (ic + 0.5);
+      c0[a] = wrap_cell(ic - 1.0, (double)N);
+      w[a][0] = (float)(0.5 * ((0.5 - d) * (0.5 - d)));
+      w[a][1] = (float)(0.75 - d * d);
+      w[a][2] = (float)(0.5 * ((0.5 + d) * (0.5 + d)));
     }
   }
   const int S1 = order, S = S1 * S1 * S1;
@@ -1312,11 +1321,11 @@ int vps_assign_expand(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
     const unsigned blocks = (unsigned)((np + 255) / 256);
     if (pos_is_f64)
       hipLaunchKernelGGL(assign_expand_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         reinterpret_cast<const double*>(pos_dev), payload_dev, (long long)np, C, N, 1.0 / lcell, lcell,
+                         reinterpret_cast<const double*>(pos_dev), payload_dev, (long long)np, C, N, lcell,
                          order, pos_out_dev, payload_out_dev);
     else
       hipLaunchKernelGGL(assign_expand_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         reinterpret_cast<const float*>(pos_dev), payload_dev, (long long)np, C, N, 1.0 / lcell, lcell,
+                         reinterpret_cast<const float*>(pos_dev), payload_dev, (long long)np, C, N, lcell,
                          order, pos_out_dev, payload_out_dev);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());

@@ -57,9 +57,18 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// LDS of hist_pairs_kernel: edges[nbins + 1] and sums[nbins] in float64, counts[nbins] in 32 bits
+size_t hist_lds_bytes(long long nbins) { return sizeof(double) * (size_t)(2 * nbins + 1) + sizeof(unsigned) * (size_t)nbins; }
+
 }  // namespace
 
 extern "C" {
+
+int vps_hist_max_bins(vps_ctx* ctx) {
+  if (!ctx) return VPS_ERR_ARG;
+  const long long m = ((long long)ctx->lds_per_block - (long long)sizeof(double)) / (long long)(2 * sizeof(double) + sizeof(unsigned));
+  return m < 0 ? 0 : (m > 0x7fffffffLL ? 0x7fffffff : (int)m);
+}
 
 int vps_pair_k(vps_ctx* ctx, int N, const double* kx_host, const double* ky_host,
                const double* kz_host, double* out_dev) {
@@ -93,8 +102,13 @@ int vps_hist_pairs(vps_ctx* ctx, const double* k_dev, const double* w_dev, int64
                    const double* edges_host, int nbins, double* psum_dev,
                    unsigned long long* nsample_dev) {
   VPS_ENTER(ctx);
-  if (n < 0 || nbins < 1 || nbins > 8192 || !edges_host || !psum_dev || !nsample_dev)
+  if (n < 0 || nbins < 1 || !edges_host || !psum_dev || !nsample_dev)
     return vps_fail(ctx, VPS_ERR_ARG, "vps_hist_pairs: bad arguments");
+  // the whole histogram of a workgroup lives in LDS: refused here, before anything is enqueued, if it cannot
+  const size_t lds = hist_lds_bytes(nbins);
+  if (nbins > vps_hist_max_bins(ctx))
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_hist_pairs: nbins=%d needs %zu B of LDS, a workgroup of this device has %zu B: at most %d bins",
+                    nbins, lds, ctx->lds_per_block, vps_hist_max_bins(ctx));
   for (int i = 0; i < nbins; ++i)
     if (!(edges_host[i] <= edges_host[i + 1]))
       return vps_fail(ctx, VPS_ERR_ARG, "vps_hist_pairs: edges must increase monotonically");
@@ -110,7 +124,13 @@ int vps_hist_pairs(vps_ctx* ctx, const double* k_dev, const double* w_dev, int64
   long long blocks = (n + 255) / 256;
   const long long cap = (long long)ctx->num_cu * 8;
   if (blocks > cap) blocks = cap;
-  const size_t lds = sizeof(double) * (2 * nbins + 1) + sizeof(unsigned) * nbins;
+  if (lds > 64 * 1024) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(hist_pairs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+      (void)hipFree(d_edges);
+      VPS_HIP_CHECK(ctx, e);
+    }
+  }
   {
     vps_launch_timer tm(ctx, VPS_K_MISC);
     hipLaunchKernelGGL(hist_pairs_kernel, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, k_dev, w_dev,

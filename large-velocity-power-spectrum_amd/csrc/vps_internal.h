@@ -28,6 +28,7 @@ struct vps_ctx {
   char err[512] = {0};
   int num_cu = 256;
   size_t lds_per_cu = 160 * 1024;
+  size_t lds_per_block = 64 * 1024;   // hipDeviceAttributeMaxSharedMemoryPerBlock, queried once (vps_create)
 
   std::map<int, vps_fft_tables> fft_tables;  // keyed by complex length NC
 

@@ -111,6 +111,7 @@ SYMBOLS = (
     ("vps_rfft3", C.c_int, (_vp, C.c_int, _vp, _vp, _vp)),
     ("vps_power_grid", C.c_int, (_vp, C.c_int, _vp, _vp, _vp)),
     ("vps_pair_k", C.c_int, (_vp, C.c_int, _dp, _dp, _dp, _vp)),
+    ("vps_hist_max_bins", C.c_int, (_vp,)),
     ("vps_hist_pairs", C.c_int, (_vp, _vp, _vp, _i64, _dp, C.c_int, _vp, _vp)),
 )
 
@@ -125,7 +126,7 @@ DEPOSIT_PLAN_FIELDS = ("bx", "by", "bz", "nbuckets", "cells", "cells_pow2", "two
 NN_PLAN_FIELDS = ("M", "ncell", "sorted", "gshift", "ngroups", "nchunks", "lds_scatter", "lds_fine")   # include/vps_hip.h: vps_nn_plan
 NN_SEARCH_KINDS = ("ring", "scatter", "column")          # include/vps_hip.h: VPS_NN_SEARCH_*
 NN_LAST_SEARCH_FIELDS = ("kind", "tiles", "radii", "open")   # include/vps_hip.h: vps_nn_last_search
-ABI_VERSION = 11  # include/vps_hip.h: VPS_ABI_VERSION
+ABI_VERSION = 12  # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

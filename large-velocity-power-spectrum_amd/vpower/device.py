@@ -237,6 +237,12 @@ class HipKernels:
         info = (C.c_int64 * 4)()
         self._chk(self.lib.vps_device_info(self.ctx, info))
         self.num_cu, self.lds_per_cu, self.wave, self.hbm_mib = (int(x) for x in info)
+        self.hist_max_bins = int(self.lib.vps_hist_max_bins(self.ctx))
+
+    def device_info(self):
+        """Device facts the host side sizes things by (vps_device_info, vps_hist_max_bins)."""
+        return {"num_cu": self.num_cu, "lds_per_cu": self.lds_per_cu, "wave": self.wave, "hbm_mib": self.hbm_mib,
+                "hist_max_bins": self.hist_max_bins}
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -841,15 +847,20 @@ class HipKernels:
                                       self._ptr(out)))
         return out
 
-    def hist_pairs(self, k, w, edges):
+    def hist_pairs(self, k, w, edges, psum=None, nsample=None):
+        """numpy.histogram(k, edges, weights=w) and the counts, ADDED to psum / nsample if given (else to zeros); at most
+        device_info()["hist_max_bins"] bins."""
         self._stream()
         edges = np.ascontiguousarray(edges, dtype=np.float64)
         nb = len(edges) - 1
-        psum = self.zeros((nb,), torch.float64)
-        ns = self.zeros((nb,), torch.int64)
+        psum = self.zeros((nb,), torch.float64) if psum is None else psum
+        ns = self.zeros((nb,), torch.int64) if nsample is None else nsample
+        if psum.shape != (nb,) or ns.shape != (nb,):
+            raise _ffi.VpsError("psum / nsample must have one entry per bin")
         self._chk(self.lib.vps_hist_pairs(self.ctx, self._ptr(k, torch.float64),
                                           self._ptr(w, torch.float64) if w is not None else None,
-                                          k.numel(), _ffi.as_dp(edges), nb, self._ptr(psum), self._ptr(ns)))
+                                          k.numel(), _ffi.as_dp(edges), nb, self._ptr(psum, torch.float64),
+                                          self._ptr(ns, torch.int64)))
         return psum, ns
 
 
