@@ -6,6 +6,7 @@
 #include <string>
 
 #include "vps_internal.h"
+#include "quantity.h"
 
 static char g_last_error[512] = "no error";
 
@@ -408,20 +409,14 @@ int vps_set_density_weight(vps_ctx* ctx, double alpha) {
 }  // extern "C"
 
 int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags) {
-  if (quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY) {
-    const char* name = quantity == VPS_DENSITY ? "VPS_DENSITY" : "VPS_LOG_DENSITY";
-    if (quantity == VPS_DENSITY && !std::isfinite(ctx->weight_alpha))
-      return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_DENSITY without an exponent (vps_set_density_weight)", who);
-    if (flags & VPS_FLAG_COMPONENT_MASK)
-      return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_FLAG_COMPONENTS with the (scalar) %s field", who, name);
-    if (flags & (VPS_FLAG_SHARE_ENERGY | VPS_FLAG_REFERENCE_MOMENTUM_BUG))
-      return vps_fail(ctx, VPS_ERR_ARG, "%s: %s takes neither VPS_FLAG_SHARE_ENERGY nor VPS_FLAG_REFERENCE_MOMENTUM_BUG", who, name);
-    return VPS_OK;
-  }
-  if (quantity != VPS_WEIGHTED_VELOCITY) return VPS_OK;
-  if (!std::isfinite(ctx->weight_alpha))
-    return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_WEIGHTED_VELOCITY without an exponent (vps_set_density_weight)", who);
+  static const char* const names[] = {"VPS_WEIGHTED_VELOCITY", "VPS_DENSITY", "VPS_LOG_DENSITY"};
+  if (!vps_quantity_needs_alpha(quantity) && !vps_quantity_scalar_rho(quantity)) return VPS_OK;
+  const char* name = names[quantity - VPS_WEIGHTED_VELOCITY];
+  if (vps_quantity_needs_alpha(quantity) && !std::isfinite(ctx->weight_alpha))
+    return vps_fail(ctx, VPS_ERR_ARG, "%s: %s without an exponent (vps_set_density_weight)", who, name);
+  if (vps_quantity_scalar_rho(quantity) && (flags & VPS_FLAG_COMPONENT_MASK))
+    return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_FLAG_COMPONENTS with the (scalar) %s field", who, name);
   if (flags & (VPS_FLAG_SHARE_ENERGY | VPS_FLAG_REFERENCE_MOMENTUM_BUG))
-    return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_WEIGHTED_VELOCITY takes neither VPS_FLAG_SHARE_ENERGY nor VPS_FLAG_REFERENCE_MOMENTUM_BUG", who);
+    return vps_fail(ctx, VPS_ERR_ARG, "%s: %s takes neither VPS_FLAG_SHARE_ENERGY nor VPS_FLAG_REFERENCE_MOMENTUM_BUG", who, name);
   return VPS_OK;
 }

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "vps_internal.h"
+#include "quantity.h"
 #include "scan.h"
 #include "bucket_sort.h"
 
@@ -405,18 +406,19 @@ __device__ __forceinline__ void algebra_cell(float a, float b, float c, float rh
 }
 
 // Density-weighted velocity w = rho^alpha v (VPS_WEIGHTED_VELOCITY), 0 where there is no mass whatever alpha is.  The power is
-// exp2(e log2 rho) on the transcendental units (v_log_f32, v_exp_f32), as in the pencil kernel (fft.hip: pencil_rho_factor):
+// exp2(e log2 rho) on the transcendental units (quantity.h: vps_rho_weight, as in the pencil kernel and the NN emit):
 //   channels [rho v, rho]:               w = (rho v) rho^(alpha - 1)
 //   VPS_FLAG_INPUT_IS_VM [v, mass]:      w = v (mass / vol)^alpha
-// A function of its own: algebra_cell and the kernels built on it stay what they were.
+// alpha - 1 is formed HERE, in float, from the float alpha; the NN and pencil routes get (float)(alpha - 1.0) from the host's
+// double.  The two differ in the last bit for some alpha (1/3): each route keeps the rounding it was introduced with.
 __device__ __forceinline__ void weighted_cell(float a, float b, float c, float rho, int flags, float vol, float alpha,
                                               float out[4]) {
   float f;
   if (flags & VPS_FLAG_INPUT_IS_VM) {
     const float r = rho * __builtin_amdgcn_rcpf(vol);
-    f = rho != 0.f ? __builtin_amdgcn_exp2f(alpha * __builtin_amdgcn_logf(r)) : 0.f;
+    f = rho != 0.f ? vps_rho_weight_nz(r, alpha) : 0.f;   // (empty means no MASS, whatever r rounds to)
   } else {
-    f = rho != 0.f ? __builtin_amdgcn_exp2f((alpha - 1.f) * __builtin_amdgcn_logf(rho)) : 0.f;
+    f = vps_rho_weight(rho, alpha - 1.f);
   }
   // (a zero factor must give 0, not NaN, for whatever the empty cell's velocity channels hold)
   out[0] = f != 0.f ? a * f : 0.f;
@@ -425,26 +427,54 @@ __device__ __forceinline__ void weighted_cell(float a, float b, float c, float r
   out[3] = 0.f;
 }
 
-// The scalar density quantities: s = rho^alpha (VPS_DENSITY; alpha = 1 is rho itself, no transcendental) or s = ln rho
-// (VPS_LOG_DENSITY), 0 where rho = 0; exp2(alpha log2 rho) (vps_rho_pow) and log2 rho * ln 2 on the transcendental units, as in
-// the pencil kernel (fft.hip: pencil_rho_scalar).  rho is channel 3 of [rho v, rho], or mass * inv_vol for a gridded field.
-__device__ __forceinline__ float density_cell(float rho, int quantity, float alpha) {
-  if (quantity == VPS_LOG_DENSITY) return rho != 0.f ? __builtin_amdgcn_logf(rho) * 0.693147180559945309f : 0.f;
-  if (alpha == 1.f) return rho;
-  return rho != 0.f ? vps_rho_pow(rho, alpha) : 0.f;
+// What one cell of `QUANT` is made of, for every kernel that forms quantities from four channels: [rho v, rho] cell totals, or
+// [v, mass] of a gridded field with VPS_FLAG_INPUT_IS_VM.  out[0 .. vps_quantity_channels(QUANT)) is the quantity.
+//   par.vol   the cell volume -- for the scalar density quantities its INVERSE (all they need one for: rho = mass * inv_vol of a
+//             [v, mass] field; rho is channel 3 itself otherwise)
+//   par.alpha the exponent of VPS_WEIGHTED_VELOCITY / VPS_DENSITY
+struct CellPar {
+  float vol, alpha;
+};
+template <int QUANT>
+__device__ __forceinline__ void cell_quantity(float a, float b, float c, float rho, int flags, CellPar par, float out[4]) {
+  static_assert(vps_quantity_valid(QUANT), "a quantity code of include/vps_hip.h");
+  if constexpr (vps_quantity_scalar_rho(QUANT)) {
+    out[0] = vps_rho_scalar((flags & VPS_FLAG_INPUT_IS_VM) ? rho * par.vol : rho, QUANT, par.alpha);
+    out[1] = out[2] = out[3] = 0.f;
+  } else if constexpr (QUANT == VPS_WEIGHTED_VELOCITY) {
+    weighted_cell(a, b, c, rho, flags, par.vol, par.alpha, out);
+  } else {
+    algebra_cell(a, b, c, rho, QUANT, flags, par.vol, out);
+  }
 }
 
-// QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count.
-// QUANT == VPS_WEIGHTED_VELOCITY, VPS_DENSITY: `vol` carries alpha instead (the epilogue needs no cell volume: rho is channel 3
-// itself); VPS_LOG_DENSITY: it is unused.
+// run-time quantity code -> template argument: f(std::integral_constant<int, QUANT>) of the (valid) code
+template <typename Fn>
+int dispatch_quantity(int quantity, Fn&& f) {
+  switch (quantity) {
+#define VPS_Q(Q) case Q: return f(std::integral_constant<int, Q>{})
+    VPS_Q(VPS_VELOCITY); VPS_Q(VPS_MOMENTUM); VPS_Q(VPS_ENERGY); VPS_Q(VPS_VM);
+    VPS_Q(VPS_WEIGHTED_VELOCITY); VPS_Q(VPS_DENSITY); VPS_Q(VPS_LOG_DENSITY);
+#undef VPS_Q
+  }
+  return VPS_ERR_ARG;
+}
+
+// QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count.  `par` is the ONE float that epilogue
+// reads (brick_par): the channels are [rho v, rho] cell totals, never [v, mass], so a quantity needs the cell volume or alpha,
+// not both.
 template <int C, int EPI, int QUANT>
 __global__ void __launch_bounds__(256)
     brick_accumulate_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start,
-                            Bricks b, long long nbricks, int flags, float vol,
+                            Bricks b, long long nbricks, int flags, float par,
                             float* __restrict__ grid) {
-  constexpr int quantity = QUANT;
-  constexpr bool SCALAR_RHO = QUANT == VPS_DENSITY || QUANT == VPS_LOG_DENSITY;
-  constexpr int NOUT = (EPI == EPI_RAW) ? C : ((QUANT == VPS_ENERGY || SCALAR_RHO) ? 1 : (QUANT == VPS_VM ? 4 : 3));
+  constexpr int NOUT = (EPI == EPI_RAW) ? C : vps_quantity_channels(QUANT);
+  // (algebra_cell reads the flags at run time, as it always did; the quantities of rho see their constant 0)
+  const int cflags = (vps_quantity_needs_alpha(QUANT) || vps_quantity_scalar_rho(QUANT)) ? 0 : flags;
+  // One float, copied into both members: every quantity here reads exactly one of them.  QUANT < VPS_WEIGHTED_VELOCITY reads
+  // par.vol (the volume) and never par.alpha; QUANT >= VPS_WEIGHTED_VELOCITY reads par.alpha and, with cflags = 0, never par.vol,
+  // which is MEANINGLESS for them here (it holds alpha).  A two-float kernel argument would move this kernel's code.
+  const CellPar cpar{par, par};
   // Persistent workgroups walk the bricks: the streaming stores of one brick stay in flight
   // while the next bucket is being accumulated, and the tile is re-zeroed as it is read.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -516,22 +546,10 @@ __global__ void __launch_bounds__(256)
           *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
           if (inside) {
             float rx[4], ry[4], rz[4], rw[4];
-            if constexpr (SCALAR_RHO) {
-              rx[0] = density_cell(c3.x, QUANT, vol);
-              ry[0] = density_cell(c3.y, QUANT, vol);
-              rz[0] = density_cell(c3.z, QUANT, vol);
-              rw[0] = density_cell(c3.w, QUANT, vol);
-            } else if constexpr (QUANT == VPS_WEIGHTED_VELOCITY) {
-              weighted_cell(c0.x, c1.x, c2.x, c3.x, 0, 1.f, vol, rx);
-              weighted_cell(c0.y, c1.y, c2.y, c3.y, 0, 1.f, vol, ry);
-              weighted_cell(c0.z, c1.z, c2.z, c3.z, 0, 1.f, vol, rz);
-              weighted_cell(c0.w, c1.w, c2.w, c3.w, 0, 1.f, vol, rw);
-            } else {
-              algebra_cell(c0.x, c1.x, c2.x, c3.x, quantity, flags, vol, rx);
-              algebra_cell(c0.y, c1.y, c2.y, c3.y, quantity, flags, vol, ry);
-              algebra_cell(c0.z, c1.z, c2.z, c3.z, quantity, flags, vol, rz);
-              algebra_cell(c0.w, c1.w, c2.w, c3.w, quantity, flags, vol, rw);
-            }
+            cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx);
+            cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry);
+            cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz);
+            cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw);
 #pragma unroll
             for (int c = 0; c < NOUT; ++c)
               {   // streaming store: the grid is written once; the cache should keep the records (-33 %)
@@ -559,12 +577,7 @@ __global__ void __launch_bounds__(256)
           for (int c = 0; c < C; ++c) grid[c * plane + cell] = v[c];
         } else {
           float r[4];
-          if constexpr (SCALAR_RHO)
-            r[0] = density_cell(v[3], QUANT, vol);
-          else if constexpr (QUANT == VPS_WEIGHTED_VELOCITY)
-            weighted_cell(v[0], v[1], v[2], v[3], 0, 1.f, vol, r);
-          else
-            algebra_cell(v[0], v[1], v[2], v[3], quantity, flags, vol, r);
+          cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r);
 #pragma unroll
           for (int c = 0; c < NOUT; ++c) grid[c * plane + cell] = r[c];
         }
@@ -574,77 +587,40 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// In-place algebra on an existing 4-channel grid (used after the NN resample and by
-// BoxField.spctrm on user-supplied fields).
+// The quantity of an existing 4-channel grid (used after the NN resample and by BoxField.spctrm on user-supplied fields): its
+// vps_quantity_channels(QUANT) channels, four cells per thread.
 // `out` == nullptr: in place; else the channels of the result go to out[c][ncell] and ch is only read
 // (a second quantity of the same field: no copy of the four input channels is needed).
+// The scalar density quantities read channel 3 alone: rho itself, or mass * inv_vol with VPS_FLAG_INPUT_IS_VM (cell_quantity).
+template <int QUANT>
 __global__ void __launch_bounds__(256)
-    field_algebra_kernel(float* ch, long long ncell, int quantity, int flags, float vol, float* out) {
+    field_quantity_kernel(float* ch, long long ncell, int flags, CellPar par, float* out) {
+  constexpr int NCH = vps_quantity_channels(QUANT);
   const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i0 >= ncell) return;
   float* dst = out ? out : ch;
-  float4 a = *reinterpret_cast<float4*>(ch + i0);
-  float4 b = *reinterpret_cast<float4*>(ch + ncell + i0);
-  float4 c = *reinterpret_cast<float4*>(ch + 2 * ncell + i0);
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
+  if constexpr (!vps_quantity_scalar_rho(QUANT)) {
+    a = *reinterpret_cast<float4*>(ch + i0);
+    b = *reinterpret_cast<float4*>(ch + ncell + i0);
+    c = *reinterpret_cast<float4*>(ch + 2 * ncell + i0);
+  }
   float4 m = *reinterpret_cast<float4*>(ch + 3 * ncell + i0);
   float r[4];
-  algebra_cell(a.x, b.x, c.x, m.x, quantity, flags, vol, r);
+  cell_quantity<QUANT>(a.x, b.x, c.x, m.x, flags, par, r);
   a.x = r[0]; b.x = r[1]; c.x = r[2]; m.x = r[3];
-  algebra_cell(a.y, b.y, c.y, m.y, quantity, flags, vol, r);
+  cell_quantity<QUANT>(a.y, b.y, c.y, m.y, flags, par, r);
   a.y = r[0]; b.y = r[1]; c.y = r[2]; m.y = r[3];
-  algebra_cell(a.z, b.z, c.z, m.z, quantity, flags, vol, r);
+  cell_quantity<QUANT>(a.z, b.z, c.z, m.z, flags, par, r);
   a.z = r[0]; b.z = r[1]; c.z = r[2]; m.z = r[3];
-  algebra_cell(a.w, b.w, c.w, m.w, quantity, flags, vol, r);
+  cell_quantity<QUANT>(a.w, b.w, c.w, m.w, flags, par, r);
   a.w = r[0]; b.w = r[1]; c.w = r[2]; m.w = r[3];
   *reinterpret_cast<float4*>(dst + i0) = a;
-  if (quantity != VPS_ENERGY) {
+  if constexpr (NCH >= 3) {
     *reinterpret_cast<float4*>(dst + ncell + i0) = b;
     *reinterpret_cast<float4*>(dst + 2 * ncell + i0) = c;
   }
-  if (quantity == VPS_VM) *reinterpret_cast<float4*>(dst + 3 * ncell + i0) = m;
-}
-
-// The density-weighted velocity of a gridded field (vps_field_algebra[_out] with VPS_WEIGHTED_VELOCITY): three channels,
-// in place or to `out`; a kernel of its own, so that field_algebra_kernel is untouched.
-__global__ void __launch_bounds__(256)
-    field_weighted_kernel(float* ch, long long ncell, int flags, float vol, float alpha, float* out) {
-  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i0 >= ncell) return;
-  float* dst = out ? out : ch;
-  float4 a = *reinterpret_cast<float4*>(ch + i0);
-  float4 b = *reinterpret_cast<float4*>(ch + ncell + i0);
-  float4 c = *reinterpret_cast<float4*>(ch + 2 * ncell + i0);
-  const float4 m = *reinterpret_cast<float4*>(ch + 3 * ncell + i0);
-  float r[4];
-  weighted_cell(a.x, b.x, c.x, m.x, flags, vol, alpha, r);
-  a.x = r[0]; b.x = r[1]; c.x = r[2];
-  weighted_cell(a.y, b.y, c.y, m.y, flags, vol, alpha, r);
-  a.y = r[0]; b.y = r[1]; c.y = r[2];
-  weighted_cell(a.z, b.z, c.z, m.z, flags, vol, alpha, r);
-  a.z = r[0]; b.z = r[1]; c.z = r[2];
-  weighted_cell(a.w, b.w, c.w, m.w, flags, vol, alpha, r);
-  a.w = r[0]; b.w = r[1]; c.w = r[2];
-  *reinterpret_cast<float4*>(dst + i0) = a;
-  *reinterpret_cast<float4*>(dst + ncell + i0) = b;
-  *reinterpret_cast<float4*>(dst + 2 * ncell + i0) = c;
-}
-
-// The scalar density quantities of a gridded field (vps_field_algebra[_out] with VPS_DENSITY / VPS_LOG_DENSITY): ONE channel,
-// in place (channel 0) or to `out`, from channel 3 alone -- rho itself, or mass * inv_vol with VPS_FLAG_INPUT_IS_VM.
-__global__ void __launch_bounds__(256)
-    field_density_kernel(float* ch, long long ncell, int quantity, int flags, float inv_vol, float alpha, float* out) {
-  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i0 >= ncell) return;
-  float* dst = out ? out : ch;
-  float4 m = *reinterpret_cast<float4*>(ch + 3 * ncell + i0);
-  if (flags & VPS_FLAG_INPUT_IS_VM) {
-    m.x *= inv_vol; m.y *= inv_vol; m.z *= inv_vol; m.w *= inv_vol;
-  }
-  m.x = density_cell(m.x, quantity, alpha);
-  m.y = density_cell(m.y, quantity, alpha);
-  m.z = density_cell(m.z, quantity, alpha);
-  m.w = density_cell(m.w, quantity, alpha);
-  *reinterpret_cast<float4*>(dst + i0) = m;
+  if constexpr (NCH == 4) *reinterpret_cast<float4*>(dst + 3 * ncell + i0) = m;
 }
 
 // [rho vx, rho vy, rho vz, rho] per particle (interp.py:199-213)
@@ -960,6 +936,20 @@ int sort_into_buckets(vps_ctx* ctx, const F* pos, const float* payload, const fl
   return VPS_OK;
 }
 
+// The float each route's kernel receives for a quantity is decided here, one function per route, and nowhere else:
+//   brick epilogue  alpha for the quantities that need it (alpha - 1 is formed on the device, in float: weighted_cell), else
+//                   the cell volume (unused by VPS_LOG_DENSITY: 0)
+//   grid kernel     the cell volume and alpha; the scalar density quantities get 1 / volume instead (CellPar)
+//   pencil launch   pencil_quantity, below; NN emit: nn.hip, nn_emit_of
+float brick_par(const vps_ctx* ctx, int quantity, float vol) {
+  return vps_quantity_needs_alpha(quantity) ? (float)ctx->weight_alpha : quantity == VPS_LOG_DENSITY ? 0.f : vol;
+}
+CellPar grid_par(const vps_ctx* ctx, int quantity, double Lcell) {
+  const double vol = Lcell * Lcell * Lcell;
+  if (vps_quantity_scalar_rho(quantity)) return CellPar{(float)(1.0 / vol), quantity == VPS_DENSITY ? (float)ctx->weight_alpha : 1.f};
+  return CellPar{(float)vol, quantity == VPS_WEIGHTED_VELOCITY ? (float)ctx->weight_alpha : 0.f};
+}
+
 template <typename F, int C, bool RHOV, int EPI>
 int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const float* rho, int64_t np, int N,
                 double Lbox, int x0, int nx, int quantity, int flags, float* grid, void* work_v) {
@@ -984,30 +974,13 @@ int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const flo
     if (per_cu < 1) per_cu = 1;
     long long grid_wg = (long long)ctx->num_cu * per_cu;
     if (grid_wg > l.nbricks) grid_wg = l.nbricks;
-#define VPS_BRICK(Q)                                                                                      \
-  hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, Q>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream, \
-                     records, start, b, l.nbricks, flags, vol, grid)
-    if (EPI == EPI_RAW || quantity == VPS_VELOCITY) VPS_BRICK(VPS_VELOCITY);
-    else if (quantity == VPS_MOMENTUM) VPS_BRICK(VPS_MOMENTUM);
-    else if (quantity == VPS_ENERGY) VPS_BRICK(VPS_ENERGY);
-    else if (quantity == VPS_WEIGHTED_VELOCITY) {
-      if constexpr (EPI == EPI_ALGEBRA) {   // (the kernel's float argument is alpha here, see brick_accumulate_kernel)
-        hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, VPS_WEIGHTED_VELOCITY>), dim3((unsigned)grid_wg), dim3(256), lds,
-                           ctx->stream, records, start, b, l.nbricks, flags, (float)ctx->weight_alpha, grid);
-      }
-    }
-    else if (quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY) {
-      if constexpr (EPI == EPI_ALGEBRA) {   // (one channel; the float argument is alpha for VPS_DENSITY)
-        if (quantity == VPS_DENSITY)
-          hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, VPS_DENSITY>), dim3((unsigned)grid_wg), dim3(256), lds,
-                             ctx->stream, records, start, b, l.nbricks, flags, (float)ctx->weight_alpha, grid);
-        else
-          hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, VPS_LOG_DENSITY>), dim3((unsigned)grid_wg), dim3(256), lds,
-                             ctx->stream, records, start, b, l.nbricks, flags, 0.f, grid);
-      }
-    }
-    else VPS_BRICK(VPS_VM);
-#undef VPS_BRICK
+    auto launch = [&](auto q) {
+      hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, decltype(q)::value>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+                         records, start, b, l.nbricks, flags, brick_par(ctx, decltype(q)::value, vol), grid);
+      return VPS_OK;
+    };
+    if constexpr (EPI == EPI_RAW) launch(std::integral_constant<int, VPS_VELOCITY>{});   // (no quantity: the one raw instantiation)
+    else if (int rcq = dispatch_quantity(quantity, launch)) return vps_fail(ctx, rcq, "deposit: quantity %d", quantity);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;
@@ -1104,7 +1077,7 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   VPS_ENTER(ctx);
   int rc = check_deposit_args(ctx, "vps_deposit_field", np, N, Lbox, x0, nx);
   if (rc) return rc;
-  if (quantity < 0 || quantity > VPS_LOG_DENSITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
+  if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
   if (flags & VPS_FLAG_INPUT_IS_VM) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_INPUT_IS_VM is meaningless here");
   if (!fields_dev || !work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))
@@ -1117,9 +1090,8 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
 
 int vps_deposit_fft_zy_supported(vps_ctx* ctx, int N, int quantity) {
   if (!ctx) return 0;
-  return (quantity == VPS_VELOCITY || quantity == VPS_MOMENTUM || quantity == VPS_ENERGY || quantity == VPS_WEIGHTED_VELOCITY ||
-          quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY) &&
-                 vps_pencil_supported(ctx, N) ? 1 : 0;
+  // (VPS_VM is four fields of two kinds: not a pencil launch)
+  return vps_quantity_valid(quantity) && quantity != VPS_VM && vps_pencil_supported(ctx, N) ? 1 : 0;
 }
 
 size_t vps_deposit_fft_zy_workspace_bytes(int64_t np, int N, int nx) {
@@ -1138,6 +1110,41 @@ size_t vps_deposit_fft_zy_workspace_bytes_shared(int64_t np, int N, int nx) {
 static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* vel_dev,
                             const float* rho_dev, int64_t np, int N, double Lbox, int x0, int nx, int quantity,
                             int flags, void* spec_dev, void* nyq_dev, void* zimg_dev, void* work_dev, int64_t np_cap = -1);
+
+// What the pencil launch of (quantity, flags) forms: the components and their record channels, the launch form, and the
+// exponent it reads -- (float)(alpha - 1.0) from the host's double for the weighted velocity, alpha for the density (alpha = 1,
+// the plain density: no per-cell function at all).
+static int pencil_quantity(vps_ctx* ctx, int quantity, int flags, PencilQuantity* pq) {
+  PencilQuantity q;
+  const int bug = (quantity == VPS_MOMENTUM) && (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG);
+  if (bug) q.chan[1] = q.chan[2] = 0;
+  q.ncomp = vps_quantity_scalar_rho(quantity) ? 1 : 3;   // (the energy launch makes its one field from three components)
+  q.divide = (quantity == VPS_MOMENTUM || vps_quantity_scalar_rho(quantity)) ? 0 : 1;
+  q.energy = quantity == VPS_ENERGY;
+  q.weighted = quantity == VPS_WEIGHTED_VELOCITY;
+  if (q.weighted) q.wexp = (float)(ctx->weight_alpha - 1.0);
+  if (quantity == VPS_LOG_DENSITY) q.scalar = PENCIL_SCALAR_LOG;
+  if (quantity == VPS_DENSITY) {
+    q.sexp = (float)ctx->weight_alpha;
+    q.scalar = q.sexp == 1.f ? PENCIL_SCALAR_RHO : PENCIL_SCALAR_POW;
+  }
+  const int only = (flags & VPS_FLAG_COMPONENT_MASK) >> 4;   // bit c: component c is wanted (VPS_FLAG_COMPONENTS); 0: all
+  if (flags & VPS_FLAG_SHARE_ENERGY) {
+    if (quantity == VPS_MOMENTUM && !bug && !only) q.with_energy = 1;
+    else if (quantity == VPS_ENERGY && (flags & VPS_FLAG_REUSE_SORT)) q.with_energy = 2;
+    else return vps_fail(ctx, VPS_ERR_ARG, "VPS_FLAG_SHARE_ENERGY: a whole momentum field (no component mask, no reference bug), then "
+                                           "the energy field with VPS_FLAG_REUSE_SORT");
+  }
+  if (only) {
+    if (quantity == VPS_ENERGY) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_fft_zy: VPS_FLAG_COMPONENTS with the (scalar) energy field");
+    const int all[3] = {q.chan[0], q.chan[1], q.chan[2]};
+    q.ncomp = 0;
+    for (int c = 0; c < 3; ++c)
+      if (only & (1 << c)) q.chan[q.ncomp++] = all[c];
+  }
+  *pq = q;
+  return VPS_OK;
+}
 
 int vps_deposit_fft_zy(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* vel_dev,
                        const float* rho_dev, int64_t np, int N, double Lbox, int x0, int nx, int quantity,
@@ -1257,38 +1264,13 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
                     : sort_rhov_records<float>(ctx, reinterpret_cast<const float*>(pos_dev), vel_dev, rho_dev, np, N, Lbox, b, work, &l, np_cap);
     if (rc) return rc;
   }
+  PencilQuantity pq;
+  if ((rc = pencil_quantity(ctx, quantity, flags, &pq))) return rc;
   const double lc = Lbox / (double)N;
-  const int bug = (quantity == VPS_MOMENTUM) && (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG);
-  int chan[3] = {0, bug ? 0 : 1, bug ? 0 : 2};
-  const bool scalar_rho = quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY;   // one field from the rho round alone
-  int ncomp = scalar_rho ? 1 : 3;
-  const int only = (flags & VPS_FLAG_COMPONENT_MASK) >> 4;   // bit c: component c is wanted (VPS_FLAG_COMPONENTS); 0: all
-  int with_energy = 0;    // VPS_FLAG_SHARE_ENERGY: 1 the momentum launch that also makes the energy field, 2 the energy call that uses it
-  if (flags & VPS_FLAG_SHARE_ENERGY) {
-    if (quantity == VPS_MOMENTUM && !bug && !only) with_energy = 1;
-    else if (quantity == VPS_ENERGY && (flags & VPS_FLAG_REUSE_SORT)) with_energy = 2;
-    else return vps_fail(ctx, VPS_ERR_ARG, "VPS_FLAG_SHARE_ENERGY: a whole momentum field (no component mask, no reference bug), then "
-                                           "the energy field with VPS_FLAG_REUSE_SORT");
-  }
-  if (only) {
-    if (quantity == VPS_ENERGY) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_fft_zy: VPS_FLAG_COMPONENTS with the (scalar) energy field");
-    const int all[3] = {chan[0], chan[1], chan[2]};
-    ncomp = 0;
-    for (int c = 0; c < 3; ++c)
-      if (only & (1 << c)) chan[ncomp++] = all[c];
-  }
   // (the sort's rank array -- one word per particle, dead once the records are in place -- is the kernel's per-record scratch)
   return vps_fft_pencil_zy(ctx, N, nx, reinterpret_cast<const unsigned*>(work + l.records),
-                           reinterpret_cast<const unsigned*>(work + l.start), reinterpret_cast<float*>(work + l.ranks), ncomp, chan,
-                           (quantity == VPS_MOMENTUM || scalar_rho) ? 0 : 1, quantity == VPS_ENERGY ? 1 : 0, (float)(lc * lc * lc),
-                           spec_dev, nyq_dev, zimg_dev ? zimg_dev : (void*)(work + l.total), with_energy,
-                           quantity == VPS_WEIGHTED_VELOCITY ? 1 : 0,
-                           quantity == VPS_WEIGHTED_VELOCITY ? (float)(ctx->weight_alpha - 1.0) : 0.f,
-                           // (alpha = 1, the plain density: no per-cell function at all)
-                           quantity == VPS_LOG_DENSITY ? PENCIL_SCALAR_LOG
-                           : quantity != VPS_DENSITY ? PENCIL_SCALAR_NONE
-                           : (float)ctx->weight_alpha == 1.f ? PENCIL_SCALAR_RHO : PENCIL_SCALAR_POW,
-                           quantity == VPS_DENSITY ? (float)ctx->weight_alpha : 1.f);
+                           reinterpret_cast<const unsigned*>(work + l.start), reinterpret_cast<float*>(work + l.ranks), pq,
+                           (float)(lc * lc * lc), spec_dev, nyq_dev, zimg_dev ? zimg_dev : (void*)(work + l.total));
 }
 
 int vps_density_velocity_vector(vps_ctx* ctx, const float* vel_dev, const float* rho_dev, int64_t np,
@@ -1343,7 +1325,7 @@ int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell, float
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,
                           int64_t ncell, float* out_dev) {
   VPS_ENTER(ctx);
-  if (quantity < 0 || quantity > VPS_LOG_DENSITY) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
   if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;
   if (ncell < 0 || (ncell & 3)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: ncell must be a multiple of 4");
   if (ncell == 0) return VPS_OK;
@@ -1352,16 +1334,12 @@ int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, c
   const unsigned blocks = (unsigned)((nthreads + 255) / 256);
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
-    if (quantity == VPS_DENSITY || quantity == VPS_LOG_DENSITY)
-      hipLaunchKernelGGL(field_density_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
-                         (long long)ncell, quantity, flags, (float)(1.0 / (Lcell * Lcell * Lcell)),
-                         quantity == VPS_DENSITY ? (float)ctx->weight_alpha : 1.f, out_dev);
-    else if (quantity == VPS_WEIGHTED_VELOCITY)
-      hipLaunchKernelGGL(field_weighted_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
-                         (long long)ncell, flags, (float)(Lcell * Lcell * Lcell), (float)ctx->weight_alpha, out_dev);
-    else
-      hipLaunchKernelGGL(field_algebra_kernel, dim3(blocks), dim3(256), 0, ctx->stream, const_cast<float*>(chans_dev),
-                         (long long)ncell, quantity, flags, (float)(Lcell * Lcell * Lcell), out_dev);
+    const int rcq = dispatch_quantity(quantity, [&](auto q) {
+      hipLaunchKernelGGL(field_quantity_kernel<decltype(q)::value>, dim3(blocks), dim3(256), 0, ctx->stream,
+                         const_cast<float*>(chans_dev), (long long)ncell, flags, grid_par(ctx, quantity, Lcell), out_dev);
+      return VPS_OK;
+    });
+    if (rcq) return vps_fail(ctx, rcq, "vps_field_algebra: quantity %d", quantity);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;

@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "vps_internal.h"
+#include "quantity.h"
 
 namespace {
 
@@ -1054,16 +1055,16 @@ struct PencilParams {
 template <bool WEIGHTED>
 __device__ __forceinline__ float pencil_rho_factor(float r, float wexp) {
   if constexpr (WEIGHTED)
-    return r != 0.f ? __builtin_amdgcn_exp2f(wexp * __builtin_amdgcn_logf(r)) : 0.f;
+    return vps_rho_weight(r, wexp);
   else
     return r != 0.f ? __builtin_amdgcn_rcpf(r) : 0.f;
 }
 
 // The per-cell value of the scalar density launches (DENSITY instantiation) from the cell's density total: rho^sexp as
-// exp2(sexp log2 rho) (vps_rho_pow), or ln rho = log2 rho * ln 2, on the same units; 0 in empty cells for both.  (The plain density,
+// exp2(sexp log2 rho), or ln rho = log2 rho * ln 2 (quantity.h: vps_rho_scalar_nz), on the same units; 0 in empty cells for both.  (The plain density,
 // PENCIL_SCALAR_RHO, never gets here: the accumulator goes into the transform as it is.)
 __device__ __forceinline__ float pencil_rho_scalar(float r, int mode, float sexp) {
-  const float s = mode == PENCIL_SCALAR_LOG ? __builtin_amdgcn_logf(r) * 0.693147180559945309f : vps_rho_pow(r, sexp);
+  const float s = vps_rho_scalar_nz(r, mode == PENCIL_SCALAR_LOG, sexp);
   return r != 0.f ? s : 0.f;
 }
 
@@ -2980,8 +2981,8 @@ bool vps_pencil_supported(vps_ctx* ctx, int N) {
 // records sorted by pencil -> ncomp half spectra after the z and y passes (spec_dev == NULL: z pass only, the
 // z images [component][B | BN] stay in bwork_dev)
 int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, const unsigned* start, float* side,
-                      int ncomp, const int* chan, int divide, int energy, float vol, void* spec_dev, void* nyq_dev,
-                      void* bwork_dev, int with_energy, int weighted, float wexp, int scalar, float sexp) {
+                      const PencilQuantity& q, float vol, void* spec_dev, void* nyq_dev, void* bwork_dev) {
+  const int ncomp = q.ncomp, divide = q.divide, energy = q.energy, with_energy = q.with_energy, weighted = q.weighted, scalar = q.scalar;
   if (scalar && (ncomp != 1 || divide || energy || with_energy || weighted))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_fft_pencil_zy: a scalar density quantity is one undivided field of its own");
   if (weighted && (!divide || energy || with_energy))
@@ -3004,7 +3005,7 @@ int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, cons
   p.nx = nx;
   p.nby = N / vps_pencil_tp(N);
   p.ncomp = ncomp;
-  for (int c = 0; c < 3; ++c) p.chan[c] = chan[c < ncomp ? c : 0];
+  for (int c = 0; c < 3; ++c) p.chan[c] = q.chan[c < ncomp ? c : 0];
   for (int c = 0; c < 4; ++c) {
     p.out[c] = Bbase + (size_t)c * (bfield + bnyq);
     p.nyq[c] = p.out[c] + bfield;
@@ -3013,9 +3014,9 @@ int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, cons
   p.energy = energy;
   p.with_energy = with_energy == 1;
   p.weighted = weighted;
-  p.wexp = wexp;
+  p.wexp = q.wexp;
   p.scalar = scalar;
-  p.sexp = sexp;
+  p.sexp = q.sexp;
   p.vol = vol;
   p.tw_stage = tz.tw_stage;
   p.tw_r2c = tz.tw_r2c;

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "vps_internal.h"
+#include "quantity.h"
 #include "scan.h"
 #include "bucket_sort.h"
 
@@ -220,16 +221,18 @@ __device__ __forceinline__ float4 srec_load(const float4* __restrict__ srec, uns
 //   NN_VELOCITY  v alone: 3 channels          NN_MOMENTUM  p = v * mass = rho v * Lcell^3 (interp.py:523-525): 3 channels
 //   NN_MOMBUG    the reference's momentum slip (py = pz = vx * mass): 3 channels
 //   NN_ENERGY    E = mass |v|^2 = Lcell^3 |rho v|^2 / rho (interp.py:546): 1 channel
-//   NN_WEIGHTED  w = rho^alpha v = rho v * rho^(alpha - 1) of the nearest particle (VPS_WEIGHTED_VELOCITY; NnEmit::vol carries
-//                alpha - 1: no cell volume enters), the power as exp2((alpha - 1) log2 rho): 3 channels
-//   NN_DENSITY   s = rho^alpha of the nearest particle (VPS_DENSITY; NnEmit::vol carries alpha; alpha = 1: rho as it is, no
-//                transcendental), NN_LOGDENS  s = ln rho = log2 rho * ln 2 (VPS_LOG_DENSITY): 1 channel each, 0 where rho = 0
+//   NN_WEIGHTED  w = rho^alpha v = rho v * rho^(alpha - 1) of the nearest particle (VPS_WEIGHTED_VELOCITY): 3 channels
+//   NN_DENSITY   s = rho^alpha of the nearest particle (VPS_DENSITY; alpha = 1: rho as it is, no transcendental),
+//   NN_LOGDENS   s = ln rho (VPS_LOG_DENSITY): 1 channel each, 0 where rho = 0
 // -- the quantity a spectrum needs, formed where the winner is known, so that neither a fourth channel nor a weighted z pass
 // moves bytes for it (C3: momentum -- 12.9 instead of 17.2 GB written, 4.3 GB less read per component in the z pass).
+// The forms keep a numbering of their own (nn_emit_of maps a quantity code and its flags to one): switching on the VPS_* codes
+// themselves moves the code of all eight C = 4 search kernels ("One quantity algebra").
 enum { NN_RAW = 0, NN_VM = 1, NN_VELOCITY = 2, NN_MOMENTUM = 3, NN_MOMBUG = 4, NN_ENERGY = 5, NN_WEIGHTED = 6, NN_DENSITY = 7,
        NN_LOGDENS = 8 };
 struct NnEmit {
-  float vol;   // Lcell^3; NN_WEIGHTED: alpha - 1, NN_DENSITY: alpha instead (those forms need no volume).  Not a member of its own: a third word in
+  float par;   // what `form` reads, decided in nn_emit_of: Lcell^3; NN_WEIGHTED: alpha - 1, NN_DENSITY: alpha (those forms need no volume).
+               // Not a member of its own: a third word in
                // this kernel argument costs nn_query_kernel<*, 4> one SGPR and nn_fallback_kernel<*, 4> one more SGPR spill
                // (measured, gfx950), and the existing search kernels are to compile exactly as before
   int form;
@@ -238,26 +241,29 @@ __host__ __device__ inline int nn_form_channels(int form, int C) {
   return form == NN_RAW ? C : form == NN_VM ? 4 : (form == NN_ENERGY || form == NN_DENSITY || form == NN_LOGDENS) ? 1 : 3;
 }
 // the 1..4 output values of one lattice point from its payload
+// The velocity, momentum, energy and VM arms are NOT deposit.hip's algebra_cell: an IEEE 1.f / rho and (rho v * inv) * (rho * vol)
+// here, v_rcp_f32 and (rho v) * vol there -- different roundings, kept apart on purpose.  The three arms of rho are the shared
+// functions of quantity.h: bit for bit what cell_quantity makes of the same [rho v, rho].
 __device__ __forceinline__ float4 nn_form_apply(float4 v, NnEmit em) {
   const float inv = v.w != 0.f ? 1.f / v.w : 0.f;
   switch (em.form) {
-    case NN_VM: return make_float4(v.x * inv, v.y * inv, v.z * inv, v.w * em.vol);
+    case NN_VM: return make_float4(v.x * inv, v.y * inv, v.z * inv, v.w * em.par);
     case NN_VELOCITY: return make_float4(v.x * inv, v.y * inv, v.z * inv, 0.f);
-    case NN_MOMENTUM: return make_float4((v.x * inv) * (v.w * em.vol), (v.y * inv) * (v.w * em.vol), (v.z * inv) * (v.w * em.vol), 0.f);
-    case NN_MOMBUG: { const float px = (v.x * inv) * (v.w * em.vol); return make_float4(px, px, px, 0.f); }
+    case NN_MOMENTUM: return make_float4((v.x * inv) * (v.w * em.par), (v.y * inv) * (v.w * em.par), (v.z * inv) * (v.w * em.par), 0.f);
+    case NN_MOMBUG: { const float px = (v.x * inv) * (v.w * em.par); return make_float4(px, px, px, 0.f); }
     case NN_ENERGY: {
       const float vx = v.x * inv, vy = v.y * inv, vz = v.z * inv;
-      return make_float4((v.w * em.vol) * ((vx * vx + vy * vy) + vz * vz), 0.f, 0.f, 0.f);
+      return make_float4((v.w * em.par) * ((vx * vx + vy * vy) + vz * vz), 0.f, 0.f, 0.f);
     }
     case NN_WEIGHTED: {
-      const float f = v.w != 0.f ? __builtin_amdgcn_exp2f(em.vol * __builtin_amdgcn_logf(v.w)) : 0.f;
+      const float f = vps_rho_weight(v.w, em.par);
       return make_float4(v.x * f, v.y * f, v.z * f, 0.f);
     }
-    case NN_DENSITY: {
-      const float s = v.w != 0.f ? vps_rho_pow(v.w, em.vol) : 0.f;
-      return make_float4(em.vol == 1.f ? v.w : s, 0.f, 0.f, 0.f);
+    case NN_DENSITY: {   // (vps_rho_scalar's selects, in the order this arm has always made them)
+      const float s = v.w != 0.f ? vps_rho_scalar_nz(v.w, false, em.par) : 0.f;
+      return make_float4(em.par == 1.f ? v.w : s, 0.f, 0.f, 0.f);
     }
-    case NN_LOGDENS: return make_float4(v.w != 0.f ? __builtin_amdgcn_logf(v.w) * 0.693147180559945309f : 0.f, 0.f, 0.f, 0.f);
+    case NN_LOGDENS: return make_float4(v.w != 0.f ? vps_rho_scalar_nz(v.w, true, 0.f) : 0.f, 0.f, 0.f, 0.f);
     default: return v;
   }
 }
@@ -1931,6 +1937,18 @@ static int nn_resample_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
                             const double* qz_host, int nqz, int x0, int nx, float* out_dev,
                             int32_t* nn_idx_dev, void* work_dev, NnEmit em);
 
+// The form and the one float the emit of (quantity, flags) receives, decided here and nowhere else: the cell volume;
+// (float)(alpha - 1.0), from the host's double, for the weighted velocity (the brick epilogue forms alpha - 1.f on the device: the
+// two differ in the last bit for some alpha, and each route keeps its own); alpha for the density.
+static NnEmit nn_emit_of(const vps_ctx* ctx, int quantity, int flags, double Lcell) {
+  static const int forms[] = {NN_VELOCITY, NN_MOMENTUM, NN_ENERGY, NN_VM, NN_WEIGHTED, NN_DENSITY, NN_LOGDENS};   // by vps_quantity
+  static_assert(sizeof(forms) / sizeof(forms[0]) == VPS_LOG_DENSITY + 1, "one form per quantity code");
+  const int form = (quantity == VPS_MOMENTUM && (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG)) ? (int)NN_MOMBUG : forms[quantity];
+  if (quantity == VPS_WEIGHTED_VELOCITY) return NnEmit{(float)(ctx->weight_alpha - 1.0), form};
+  if (quantity == VPS_DENSITY) return NnEmit{(float)ctx->weight_alpha, form};
+  return NnEmit{(float)(Lcell * Lcell * Lcell), form};
+}
+
 int vps_nn_resample(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* payload_dev,
                     int64_t np, int C, const double* qx_host, int nqx, const double* qy_host, int nqy,
                     const double* qz_host, int nqz, int x0, int nx, float* out_dev,
@@ -1946,26 +1964,10 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
                              float* out_dev, int32_t* nn_idx_dev, void* work_dev) {
   VPS_ENTER(ctx);
   if (!(Lcell > 0) || !out_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: bad Lcell / null output");
-  int form;
-  switch (quantity) {
-    case VPS_VM: form = NN_VM; break;
-    case VPS_VELOCITY: form = NN_VELOCITY; break;
-    case VPS_MOMENTUM: form = (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG) ? NN_MOMBUG : NN_MOMENTUM; break;
-    case VPS_ENERGY: form = NN_ENERGY; break;
-    case VPS_WEIGHTED_VELOCITY: form = NN_WEIGHTED; break;
-    case VPS_DENSITY: form = NN_DENSITY; break;
-    case VPS_LOG_DENSITY: form = NN_LOGDENS; break;
-    default: return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: quantity %d", quantity);
-  }
+  if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: quantity %d", quantity);
   if (int rc = vps_check_weighted(ctx, "vps_nn_resample_quantity", quantity, flags)) return rc;
-  if (form == NN_DENSITY)
-    return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
-                            out_dev, nn_idx_dev, work_dev, NnEmit{(float)ctx->weight_alpha, form});
-  if (form == NN_WEIGHTED)
-    return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
-                            out_dev, nn_idx_dev, work_dev, NnEmit{(float)(ctx->weight_alpha - 1.0), form});
   return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
-                          out_dev, nn_idx_dev, work_dev, NnEmit{(float)(Lcell * Lcell * Lcell), form});
+                          out_dev, nn_idx_dev, work_dev, nn_emit_of(ctx, quantity, flags, Lcell));
 }
 
 int vps_nn_resample_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* rhov_dev,
@@ -1975,7 +1977,7 @@ int vps_nn_resample_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, con
   VPS_ENTER(ctx);
   if (!(Lcell > 0) || !out_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_field: bad Lcell / null output");
   return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
-                          out_dev, nn_idx_dev, work_dev, NnEmit{(float)(Lcell * Lcell * Lcell), NN_VM});
+                          out_dev, nn_idx_dev, work_dev, nn_emit_of(ctx, VPS_VM, 0, Lcell));
 }
 
 static int nn_resample_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* payload_dev,

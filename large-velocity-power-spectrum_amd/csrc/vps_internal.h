@@ -131,21 +131,7 @@ struct vps_launch_timer {
 };
 
 // The scalar density launches of the pencil kernel (VPS_DENSITY, VPS_LOG_DENSITY): one accumulation round of rho, then the
-// per-cell function of it -- none (alpha = 1: the cell total as it is), rho^sexp, or ln rho.
-// rho^a of the scalar density quantity for rho > 0 (the callers select 0 where rho = 0): exp2(a log2 rho) on the transcendental
-// units (v_log_f32, v_exp_f32) with rho's binary exponent taken out first -- rho = m 2^e, m in [0.5, 1), so
-// a log2 rho = n + (a e - n) + a log2 m with n = rint(a e): the logarithm's result and the argument of exp2 stay of order 1,
-// where one ulp is 6e-8, instead of carrying one ulp of |log2 rho| (1e-6 at 2^13) into the exponent.  A positive field has a
-// mean: a one-sided ulp of the straight form times that mean was 7e-6 of the rms in the thin-slab images.
-#if defined(__HIPCC__)
-__device__ __forceinline__ float vps_rho_pow(float r, float a) {
-  const float e = (float)__builtin_amdgcn_frexp_expf(r);
-  const float n = __builtin_rintf(a * e);
-  const float f = __builtin_fmaf(a, e, -n) + a * __builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(r));
-  return __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
-}
-#endif
-
+// per-cell function of it (quantity.h: vps_rho_scalar_nz) -- none (alpha = 1: the cell total as it is), rho^sexp, or ln rho.
 enum { PENCIL_SCALAR_NONE = 0, PENCIL_SCALAR_RHO = 1, PENCIL_SCALAR_POW = 2, PENCIL_SCALAR_LOG = 3 };
 
 // fft.hip
@@ -157,11 +143,21 @@ void vps_fft_free_tables(vps_ctx* ctx);
 // fused deposit -> z pass ("pencil" path): records sorted by pencil -> ncomp half spectra
 int vps_pencil_tp(int N);
 bool vps_pencil_supported(vps_ctx* ctx, int N);
+// What a pencil launch forms from the [rho v, rho] records: filled from (quantity, flags) in ONE place (deposit.hip:
+// pencil_quantity), copied member by member into the kernel argument (fft.hip: PencilParams, whose layout does not change).
+struct PencilQuantity {
+  int ncomp = 3;
+  int chan[3] = {0, 1, 2};             // record channel (0..2) feeding component c
+  int divide = 0, energy = 0;          // PencilParams
+  int with_energy = 0;                 // VPS_FLAG_SHARE_ENERGY: 1 the momentum launch that also makes the energy field, 2 the energy call that uses it
+  int weighted = 0;                    // q * rho^wexp
+  float wexp = 0.f;
+  int scalar = PENCIL_SCALAR_NONE;
+  float sexp = 1.f;
+};
 // side: one float per record (scratch of the kernel: what it keeps per record when a bucket outgrows its registers)
 int vps_fft_pencil_zy(vps_ctx* ctx, int N, int nx, const unsigned* records, const unsigned* start, float* side,
-                      int ncomp, const int* chan, int divide, int energy, float vol, void* spec_dev, void* nyq_dev,
-                      void* bwork_dev, int with_energy = 0, int weighted = 0, float wexp = 0.f,   // weighted: q * rho^wexp
-                      int scalar = PENCIL_SCALAR_NONE, float sexp = 1.f);
+                      const PencilQuantity& q, float vol, void* spec_dev, void* nyq_dev, void* bwork_dev);
 
 // ---- LDS floating-point accumulation ---------------------------------------------------------
 // gfx950 executes ds_add_f32 far below the LDS rate (measured: about one lane every two clocks per

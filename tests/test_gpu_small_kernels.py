@@ -392,3 +392,111 @@ def test_density_velocity_vector_bit_exact(K, T, particles, count):
     ref = orc.density_velocity_vector(vel[:n], rho[:n])
     assert ref.dtype == np.float32 and np.array_equal(got, ref)
     assert np.array_equal(got[:, :3], vel[:n] * rho[:n, None]) and np.array_equal(got[:, 3], rho[:n])
+
+
+# ---- one per-cell quantity algebra (csrc/quantity.h, deposit.hip: cell_quantity) --------------------------------------------------
+# The brick epilogue, the grid kernel and the rho arms of the NN emit form a quantity through the same inline functions, so two
+# routes that reach them with the same [rho v, rho] must agree bit for bit -- nothing here needs a tolerance.
+def _quantities():
+    from vpower import device as D
+    return [("velocity", D.VELOCITY, 0), ("momentum", D.MOMENTUM, 0), ("momentum_bug", D.MOMENTUM, D.FLAG_REFERENCE_MOMENTUM_BUG),
+            ("energy", D.ENERGY, 0), ("vm", D.VM, 0), ("weighted_third", D.WeightedVelocity(1.0 / 3.0), 0),
+            ("weighted_minus_half", D.WeightedVelocity(-0.5), 0), ("density_1", D.Density(1.0), 0),
+            ("density_half", D.Density(0.5), 0), ("log_density", D.LOG_DENSITY, 0)]
+
+
+QUANTITY_IDS = [q[0] for q in _quantities()]
+
+
+def _integer_particles(N, seed):
+    """Integer-valued rho and v (cell totals are exact whatever the order of the LDS adds), a grid sparse enough to leave empty
+    cells, a handful of particles without density."""
+    rng = np.random.default_rng(seed)
+    n = N ** 3 // 2
+    pos = rng.random((n, 3)).astype(np.float32)
+    vel = rng.integers(-4, 5, (n, 3)).astype(np.float32)
+    rho = rng.integers(1, 6, n).astype(np.float32)
+    rho[:: n // 7] = 0.0
+    return pos, vel, rho
+
+
+@pytest.fixture(scope="module")
+def raw_grids(K):
+    """N -> (particles on the device, the raw four-channel deposit of [rho v, rho]); computed once, never written to."""
+    out = {}
+    for N in (10, 16):
+        pos, vel, rho = _integer_particles(N, 300 + N)
+        dp, dv, dr = K.to_device(pos), K.to_device(vel), K.to_device(rho)
+        raw = K.deposit(dp, K.density_velocity_vector(dv, dr), N, 1.0, 0, N).clone()
+        assert int((raw[3] == 0).sum()) > N, "the grid is meant to have empty cells"
+        out[N] = (dp, dv, dr, raw)
+    return out
+
+
+@pytest.mark.parametrize("N", [10, 16])       # 10: the brick kernel's scalar stream-out; 16: its vec4 path, partial bricks
+@pytest.mark.parametrize("name", QUANTITY_IDS)
+def test_deposit_field_is_deposit_then_field_algebra(K, raw_grids, name, N):
+    from vpower import device as D
+    _, q, flags = _quantities()[QUANTITY_IDS.index(name)]
+    dp, dv, dr, raw = raw_grids[N]
+    fused = K.deposit_field(dp, dv, dr, N, 1.0, 0, N, q, flags)
+    grid = raw.clone()
+    K.field_algebra(grid, q, flags, 1.0 / N)
+    assert fused.shape[0] == D.NCOMP[int(q)]
+    assert torch.equal(fused, grid[: fused.shape[0]])
+
+
+@pytest.mark.parametrize("vm", [0, 1], ids=["rhov", "input_is_vm"])
+@pytest.mark.parametrize("N", [10, 16])       # 10: 250 threads, a partial (and only) block
+@pytest.mark.parametrize("name", QUANTITY_IDS)
+def test_field_algebra_in_place_is_field_algebra_out(K, raw_grids, name, N, vm):
+    from vpower import device as D
+    _, q, flags = _quantities()[QUANTITY_IDS.index(name)]
+    flags |= D.FLAG_INPUT_IS_VM if vm else 0
+    rng = np.random.default_rng(17 + N)
+    chans = raw_grids[N][3].clone()
+    chans[:3] += K.to_device(rng.standard_normal((3, N, N, N)).astype(np.float32))     # float data: no atomics on this route
+    chans[3] *= K.to_device(np.exp(rng.standard_normal((N, N, N))).astype(np.float32))
+    keep = chans.clone()
+    out = K.field_algebra_out(chans, q, flags, 1.0 / N)
+    assert torch.equal(chans, keep), "field_algebra_out only reads its input"
+    K.field_algebra(chans, q, flags, 1.0 / N)
+    n = D.NCOMP[int(q)]
+    assert out.shape[0] == n and torch.equal(chans[:n], out)
+    assert torch.equal(chans[n:], keep[n:]), "the channels a quantity does not have stay what they were"
+
+
+@pytest.fixture(scope="module")
+def nn_inputs(K):
+    rng = np.random.default_rng(91)
+    n, N = 20000, 32
+    pos = rng.random((n, 3)).astype(np.float32)
+    vel = rng.standard_normal((n, 3)).astype(np.float32)
+    rho = np.exp(0.5 * rng.standard_normal(n)).astype(np.float32)
+    rho[:: n // 9] = 0.0
+    dp = K.to_device(pos)
+    pay = K.density_velocity_vector(K.to_device(vel), K.to_device(rho))
+    ax = orc.lattice_axes_library(1.0, N)
+    return dp, pay, (ax, ax, ax), N
+
+
+# (the grid route forms alpha - 1 on the device in float, the NN route takes it from the host's double: the weighted velocity at
+# exponents whose two forms of alpha - 1 agree)
+@pytest.mark.parametrize("kernel", ["column", "query_centric"])
+@pytest.mark.parametrize("name", ["weighted_half", "weighted_minus_half", "density_1", "density_half", "log_density"])
+def test_nn_quantity_is_nn_payload_then_field_algebra(K, nn_inputs, name, kernel):
+    from vpower import _ffi, device as D
+    q = {"weighted_half": D.WeightedVelocity(0.5), "weighted_minus_half": D.WeightedVelocity(-0.5), "density_1": D.Density(1.0),
+         "density_half": D.Density(0.5), "log_density": D.LOG_DENSITY}[name]
+    dp, pay, axes, N = nn_inputs
+    opt = "nn_column" if kernel == "column" else "nn_query_centric"
+    _ffi.set_option(opt, 1)
+    try:
+        direct, i1 = K.nn_resample_quantity(dp, pay, axes, 0, N, 1.0 / N, q, want_index=True)
+        assert K.nn_last_search()["kind"] == ("column" if kernel == "column" else "ring"), "the option did not select the search"
+        raw, i0 = K.nn_resample(dp, pay, axes, 0, N, want_index=True)
+    finally:
+        _ffi.set_option(opt, None)
+    assert torch.equal(i0, i1)
+    assert int((raw[3] == 0).sum()) > 0, "some lattice points are meant to have a nearest particle without density"
+    assert torch.equal(direct, K.field_algebra_out(raw, q, 0, 1.0 / N))
