@@ -566,3 +566,149 @@ def nn_search_kind(lattice, opts):
     if lattice[0] == "jittered" or opts.get("nn_query_centric"):
         return "ring"
     return "scatter" if opts.get("nn_column") == 0 else "column"
+
+
+# --------------------------------------------------------------------------- #
+# Custom k ranges: the table of tests/test_gpu_krange_matrix.py and the host-side rules it holds the library to
+# --------------------------------------------------------------------------- #
+# name -> (flavour, (kmin, kmax, kres) in units of kf = 2 pi / L as a function of h = N / 2).  What each row reaches:
+#   deep    most planes without a kept row (cut -1): whole tiles and planes skipped
+#   band    modes below the first edge, the float guess clamped at both ends, generic edges
+#   zero    first edge exactly 0 (np.histogram counts the k = 0 mode in bin 0), every edge on an integer multiple of kf
+#   corner  all_mode_k_range: nothing cut, a packed scope whose slots all fall back to N rows
+#   fine    several shells per kx step, nbins ~ 0.68 N
+#   many    nbins ~ N, every bin well filled: LDS offsets far from the default
+#   wide    2 bins of millions of modes each: partial counts and the reduction
+K_RANGES = {
+    "deep": ("script", lambda h: (1.0, float(round(0.3 * h)), 1.0)),
+    "band": ("library", lambda h: (0.25 * h, 0.6 * h, 1.7)),
+    "zero": ("library", lambda h: (0.5, float(h), 1.0)),
+    "corner": ("script", None),
+    "fine": ("library", lambda h: (1.0, 0.5 * h, 0.37)),
+    "many": ("script", lambda h: (0.25 * h, 0.5 * h, 0.13)),
+    "wide": ("script", lambda h: (0.3 * h, 0.8 * h, 0.5 * h)),
+}
+
+
+def k_range(name, N, L):
+    """(flavour, kmin, kmax, kres) of row `name` of K_RANGES on an N^3 grid of box length L."""
+    flavour, f = K_RANGES[name]
+    if f is None:
+        return (flavour,) + tuple(all_mode_k_range(N, L))
+    kf = 2 * np.pi / L
+    return (flavour,) + tuple(x * kf for x in f(N // 2))
+
+
+def k_range_edges(name, N, L):
+    """(centres, edges) of the row with the reference's own numpy expressions (orc.edges_library: interp.py:1472-1473,
+    orc.edges_script: parallel_optimized.py:178-180), or None where np.arange leaves centres and edges inconsistent."""
+    from oracle import vps_oracle as orc
+    flavour, kmin, kmax, kres = k_range(name, N, L)
+    centers, edges = (orc.edges_library if flavour == "library" else orc.edges_script)(kmin, kmax, kres)
+    return (centers, edges) if len(edges) == len(centers) + 1 else None
+
+
+K_ROUTE_ROWS = ("deep", "zero", "fine")     # the rows BoxField.spctrm / helmholtz_spctrm are given (library flavour there)
+
+
+def k_range_box(name, N):
+    """Box length of the row at N: 1, or 2.5 where np.arange leaves the library flavour's centres and edges inconsistent at 1
+    -- asked of the library-flavour rows and of K_ROUTE_ROWS, which the user-facing routes bin with the library flavour
+    whatever the table says (`deep` takes 2.5 at N = 192; at 2.5 it would fail at N = 1024)."""
+    from oracle import vps_oracle as orc
+    for L in (1.0, 2.5):
+        flavour, kmin, kmax, kres = k_range(name, N, L)
+        if flavour == "library" or name in K_ROUTE_ROWS:
+            centers, edges = orc.edges_library(kmin, kmax, kres)
+            if len(edges) != len(centers) + 1:
+                continue
+        if k_range_edges(name, N, L) is not None:
+            return L
+    raise AssertionError((name, N))
+
+
+def expected_binning_mode(N, k2_axis, thr, edges):
+    """The binning mode include/vps_hip.h documents for vps_set_binning, restated: 0 general shell walk, 1 mirrored kx with
+    float64 k^2 sums, 2 integer shells.  Mirrored kx needs an even N, k2[N - i] == k2[i], k2 non-decreasing up to N/2 and the
+    double-precision guess (sqrt(thr[i]) - edges[0]) / spacing within 1e-3 of i at every threshold (spacing = the mean bin
+    width).  Integer shells need, on top, k2[i] = i^2 k2[1] to 1e-12 and no thr[b] / k2[1] within 1e-9 (relative, floor 1) of an
+    integer (a threshold ON a mode: float64 rounding decides)."""
+    k2 = np.asarray(k2_axis, dtype=np.float64)
+    thr = np.asarray(thr, dtype=np.float64)
+    nb = len(thr) - 1
+    h = N // 2
+    inv = nb / (float(edges[-1]) - float(edges[0]))
+    if N % 2 or any(k2[N - i] != k2[i] for i in range(1, h)) or np.any(np.diff(k2[: h + 1]) < 0):
+        return 0
+    if np.any(np.abs((np.sqrt(thr) - float(edges[0])) * inv - np.arange(nb + 1)) >= 1e-3):
+        return 0
+    i2 = np.arange(h + 1, dtype=np.float64) ** 2
+    if not (k2[0] == 0.0 and k2[1] > 0 and np.all(np.abs(k2[: h + 1] - i2 * k2[1]) <= 1e-12 * i2 * k2[1])):
+        return 1
+    q = thr / k2[1]
+    pos = q[q > 0]
+    if np.any(pos >= 4.0e9) or np.any(np.abs(pos - np.rint(pos)) <= 1e-9 * np.maximum(pos, 1.0)):
+        return 1
+    return 2
+
+
+def row_cut(N, k2_axis, thr):
+    """The row cut of a binning-only scope (include/vps_hip.h: vps_set_bin_only), restated: per plane kz = 0..N/2 the largest
+    |ky| with a mode inside the last edge -- not fl(k2[ky] + k2[kz]) >= thr[nbins] -- rounded up to 16 k + 15 and capped at
+    N/2; -1 for a plane no shell reaches.  (The library keeps one from N = 128 on, under the mirrored-kx modes.)"""
+    k2 = np.asarray(k2_axis, dtype=np.float64)
+    h = N // 2
+    out = np.full(h + 1, -1, dtype=np.int64)
+    for kz in range(h + 1):
+        ok = np.nonzero(~((k2[: h + 1] + k2[kz]) >= thr[-1]))[0]
+        if len(ok):
+            out[kz] = min(int(ok[-1]) | 15, h)
+    return out
+
+
+def slot_cuts(kcut, N, G, C):
+    """[chunk][slot] -> the cuts of the G planes that share the slot: slot j of rank r in chunk c is plane c G nkc + j G + r
+    (nkc = N / 2 / G / C; include/vps_hip.h: vps_fft_y)."""
+    nkc = N // 2 // G // C
+    return [[[int(kcut[c * G * nkc + j * G + r]) for r in range(G)] for j in range(nkc)] for c in range(C)]
+
+
+def slot_rows(cuts, N):
+    """Rows a packed slot carries: 2 kc + 1 with kc = the largest cut of its planes, floored at 0 -- or all N rows."""
+    kc = max(max(cuts), 0)
+    return N if 2 * kc + 1 >= N else 2 * kc + 1
+
+
+def packed_block(kcut, N, nx, G, C, chunk):
+    """Elements of one destination's block of a packed chunk: the rows of its slots times nx, plus (last chunk) the rank's
+    N / G rows of the Nyquist plane."""
+    rows = sum(slot_rows(s, N) for s in slot_cuts(kcut, N, G, C)[chunk])
+    return rows * nx + ((N // G) * nx if chunk == C - 1 else 0)
+
+
+def slot_mix(kcut, N, G, C):
+    """Counts of the slot kinds the packed layout has to get right -> dict(mixed: a dead plane (-1) next to live ones,
+    dead: every plane dead, unequal: live planes with different cuts, full: slots of N rows, slots: all)."""
+    out = dict(mixed=0, dead=0, unequal=0, full=0, slots=0)
+    for chunk in slot_cuts(kcut, N, G, C):
+        for s in chunk:
+            out["slots"] += 1
+            live = [c for c in s if c >= 0]
+            out["dead"] += not live
+            out["mixed"] += bool(live) and len(live) < len(s)
+            out["unequal"] += len(set(s)) > 1
+            out["full"] += slot_rows(s, N) == N
+    return out
+
+
+# The legs of tests/test_gpu_krange_matrix.py; tests/test_separable_reference.py asserts what every (N, row) is there for
+K_WHOLE = {64: tuple(K_RANGES), 128: tuple(K_RANGES), 192: tuple(K_RANGES), 250: tuple(K_RANGES), 256: tuple(K_RANGES),
+           1024: ("deep", "zero", "many", "wide")}
+K_HELMHOLTZ = {128: tuple(K_RANGES), 192: tuple(K_RANGES), 250: tuple(K_RANGES), 1024: ("deep", "zero")}
+K_WINDOW = {256: ("deep", "band"), 1024: ("deep", "band")}
+K_SLABS = ((128, 4, 2), (192, 4, 3), (250, 5, 5), (256, 8, 2), (1024, 16, 2))      # (N, ranks, kz chunks)
+K_SLAB_ROWS = ("deep", "band", "zero", "corner")
+# rows whose edges fall on integer multiples of kf: integer shells must be refused (mode 1); every other (row, N) takes mode 2.
+# `deep` at N = 128, L = 1: (19 kf - kf) / kf = 17.999999999999996, so the script flavour's int() gives 18 bins over 19 kf
+# (the reference's quirk Q2, SURVEY.md) and edge 9 sits on 10 kf
+K_MODE1 = {("zero", N) for N in (64, 128, 192, 250, 256, 1024)} | {("band", 250), ("many", 64), ("many", 128), ("deep", 128)}
