@@ -16,7 +16,7 @@
 //                the WHOLE tile out with full-width coalesced stores (rows of bz cells), applying the
 //                field algebra (v = rho v / rho, momentum, kinetic energy) on the way out
 //                (brick_accumulate_kernel), or feeds it straight into the z-pass FFT
-//                (pencil_fft_z_kernel, fft.hip).
+//                (pencil_fft_z_kernel, fft_pencil.h).
 // Every cell of the slab is therefore written exactly once by plain stores: there is no
 // grid memset, no global float atomic and no separate algebra pass.
 //

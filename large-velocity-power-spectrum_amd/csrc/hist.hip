@@ -1,7 +1,7 @@
 // Un-fused forms of the binning stage, kept so that the reference's two-step API
 // (_pair_power then _hist_sample, vpower/interp.py:1440-1482; pair_power / hist_sample,
 // scripts/parallel_optimized.py:145-190) has a device implementation too.  The hot path
-// never materialises these arrays: it bins straight out of the x pass (fft.hip).
+// never materialises these arrays: it bins straight out of the x pass (fft_xpass.h).
 #pragma clang fp contract(off)
 
 #include "vps_internal.h"

@@ -1,7 +1,7 @@
 // What a quantity (include/vps_hip.h: vps_quantity) is, once: its channels, whether it is a scalar of rho, whether it needs the
 // exponent of vps_set_density_weight -- and the two functions of rho that the density-weighted velocity and the scalar density
 // quantities are made of.  Shared by the brick / grid epilogues (deposit.hip), the NN emit (nn.hip) and the pencil kernel
-// (fft.hip).  A new quantity starts here: its code in these four helpers, then its per-cell body in deposit.hip's cell_quantity.
+// (fft_pencil.h).  A new quantity starts here: its code in these four helpers, then its per-cell body in deposit.hip's cell_quantity.
 // Not part of the ABI.
 #pragma once
 #include "../../include/vps_hip.h"

@@ -39,7 +39,7 @@ struct vps_ctx {
   double* d_thr = nullptr;  // [nbins+1]
   double edge0 = 0.0, inv_spacing = 0.0;
   bool bin_fast = false;    // k2 table symmetric and monotone: mirrored-kx binning is valid
-  // integer shells (fft.hip: FASTMODE 2): k2[i] = i^2 k2[1] to rounding and no threshold within 1e-9 of an integer multiple of
+  // integer shells (fft_xpass.h: FASTMODE 2): k2[i] = i^2 k2[1] to rounding and no threshold within 1e-9 of an integer multiple of
   // k2[1] -- then nthr[b] = ceil(thr[b] / k2[1]) decides every mode exactly like the float64 comparison
   bool bin_int = false;
   unsigned* d_nthr = nullptr;   // [nbins + 1]
@@ -144,7 +144,7 @@ void vps_fft_free_tables(vps_ctx* ctx);
 int vps_pencil_tp(int N);
 bool vps_pencil_supported(vps_ctx* ctx, int N);
 // What a pencil launch forms from the [rho v, rho] records: filled from (quantity, flags) in ONE place (deposit.hip:
-// pencil_quantity), copied member by member into the kernel argument (fft.hip: PencilParams, whose layout does not change).
+// pencil_quantity), copied member by member into the kernel argument (fft_params.h: PencilParams, whose layout does not change).
 struct PencilQuantity {
   int ncomp = 3;
   int chan[3] = {0, 1, 2};             // record channel (0..2) feeding component c

@@ -15,7 +15,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 CSRC = os.path.join(PKG_ROOT, "csrc")
 LIB_PATH = os.environ.get("VPS_LIB_PATH") or os.path.join(_HERE, "libvps_hip.so")  # override: experiments only
-SOURCES = ("api.hip", "deposit.hip", "nn.hip", "fft.hip", "hist.hip", "preprocess.hip", "comm.hip")
+SOURCES = ("api.hip", "deposit.hip", "nn.hip", "fft.hip", "fft_parts.hip", "hist.hip", "preprocess.hip", "comm.hip")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics")
 
 # every symbol include/vps_hip.h declares: (name, restype, argtypes)
@@ -127,7 +127,7 @@ NN_PLAN_FIELDS = ("M", "ncell", "sorted", "gshift", "ngroups", "nchunks", "lds_s
 NN_SEARCH_KINDS = ("ring", "scatter", "column")          # include/vps_hip.h: VPS_NN_SEARCH_*
 NN_LAST_SEARCH_FIELDS = ("kind", "tiles", "radii", "open")   # include/vps_hip.h: vps_nn_last_search
 ABI_VERSION = 12  # include/vps_hip.h: VPS_ABI_VERSION
-FFT_PARTS = 4   # fft.hip is compiled once per family of line lengths (-DVPS_FFT_PART=k)
+FFT_PARTS = 4   # fft_parts.hip (the FFT's kernels) is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 
 class VpsError(RuntimeError):
@@ -161,8 +161,8 @@ def build(force=False, verbose=False):
     units = []
     for s in srcs:
         stem = os.path.basename(s).replace(".hip", "")
-        if stem == "fft":
-            # one object per family of line lengths (fft.hip: "translation-unit split"), compiled side by side
+        if stem == "fft_parts":
+            # one object per family of line lengths (fft_params.h: FftPart), compiled side by side
             units += [(s, os.path.join(objdir, "fft_p%d.o" % k), ["-DVPS_FFT_PART=%d" % k]) for k in range(FFT_PARTS)]
         elif stem == "nn":
             # the device assembly is kept for the static check of the hand-made LDS pipeline (vpower/_asmcheck.py)

@@ -366,7 +366,7 @@ def test_more_than_8192_bins_are_refused_and_leave_the_tables_alone(K):
 
 def test_x_pass_beyond_the_lds_is_refused_and_leaves_the_accumulators_alone(K):
     """8192 bins under no_int_binning: the float64 threshold table, the shell sums and the counts alone need
-    (8192 + 2) * 8 + 8192 * 8 + 8192 * 4 B of LDS (launch_x in fft.hip) before any line buffer -- more than the device has.
+    (8192 + 2) * 8 + 8192 * 8 + 8192 * 4 B of LDS (launch_x in fft_xpass.h) before any line buffer -- more than the device has.
     The x pass raises "needs ... LDS", the accumulators keep their contents, and a default-range spectrum on the same context
     afterwards is correct."""
     from vpower import device, _ffi

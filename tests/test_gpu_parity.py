@@ -327,7 +327,7 @@ def test_general_binning_path_matches_fast_path(K, N, L):
 
 @pytest.mark.parametrize("N,L", [(32, 1.0), (64, 2.5), (256, 1.0), (512, 1.0)])
 def test_integer_shells_equal_float64_shells(K, N, L):
-    """Mirrored-kx binning with INTEGER shells (fft.hip FASTMODE 2: ix^2 + iy^2 + iz^2 against ceil(thr / k2[1])) -- taken
+    """Mirrored-kx binning with INTEGER shells (fft_xpass.h FASTMODE 2: ix^2 + iy^2 + iz^2 against ceil(thr / k2[1])) -- taken
     wherever vps_set_binning finds no threshold on an integer multiple of k2[1], which covers both reference flavours (edges at
     half-integer multiples of 2 pi / L, interp.py:1472-1473 / script:178-180) -- decides every mode exactly like the float64
     comparison of k^2 sums: same counts bit for bit as the float64 path AND as the oracle's np.histogram.  Edges ON integer
