@@ -77,7 +77,7 @@ int vps_destroy(vps_ctx* ctx);
 const char* vps_last_error(const vps_ctx* ctx);   /* ctx may be NULL: global slot */
 int vps_set_stream(vps_ctx* ctx, void* hip_stream);
 int vps_sync(vps_ctx* ctx);
-#define VPS_ABI_VERSION 12
+#define VPS_ABI_VERSION 13
 int vps_version(void);                            /* ABI version (VPS_ABI_VERSION)  */
 /* Tuning / test switches, process-wide.  The library never reads the environment: a stray variable in a user's job cannot
  * change a code path; the host sets what it wants explicitly (vpower/_ffi.py maps VPS_OPT_<NAME> variables once, at load,
@@ -222,6 +222,40 @@ int vps_deposit_fft_zy(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const 
  * vps_deposit_ngp gives the CIC / TSC grid; with replicated particles every slab gets its contributions without a halo. */
 int vps_assign_expand(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* payload_dev, int64_t np,
                       int C, int N, double Lbox, int order, float* pos_out_dev, float* payload_out_dev);
+
+/* Higher-order assignment, direct (ABI 13): the CIC / TSC grid of vps_assign_expand + vps_deposit_ngp from ONE record per
+ * particle.  A particle is sorted (the two-level bucket sort of the NGP route) into the brick of its base cell c0 -- the lowest
+ * cell it touches per axis: floor(s - 1/2) for CIC, floor(s) - 1 for TSC, s = (double)pos / (Lbox / N), periodic -- with a
+ * record {cell-in-brick, payload[C], 6 weight words}: per axis two float32 numbers each rounded once from float64 (CIC 1 - f
+ * and f; TSC a = 1/2 - d and b = 1/2 + d, the weights being a a / 2, 1/2 + a b, b b / 2), so that a small weight keeps its
+ * relative precision.  The brick that OWNS a cell gathers: it walks its own bucket and those of the bricks holding the
+ * order - 1 cells below its range on every axis (at most 8 buckets unless a partial last brick is narrower than that), adding
+ * payload wx wy wz in LDS for the targets (c0 + j) mod N inside its own range.  Every (particle, offset) pair is counted
+ * exactly once and grid_dev [C][N][N][N] float32 is OVERWRITTEN, every cell exactly once, by plain stores: no memset, no global
+ * float atomic.  Sums agree with the expansion route up to float32 summation order.
+ *   - the whole grid only (x0 = 0, nx = N); slabs keep the expansion route, which needs no halo exchange with replicated
+ *     particles.  C in {1, 3, 4}, order 2 (CIC) or 3 (TSC); raw channels out (vps_field_algebra makes quantities of them).
+ *   - a position whose s is NaN or infinite, or beyond 2^53 cells, is SKIPPED (it deposits nowhere); positions any finite
+ *     distance outside the box below that wrap periodically like the oracle's int64 %.
+ *   - np = 0 writes zeros.  Bad np / N / Lbox / C / order and null buffers: VPS_ERR_ARG with a message.
+ * work_dev: vps_deposit_assign_workspace_bytes(np, C, N, order) bytes (0: bad arguments): records of C + 7 words, twice, plus
+ * 12 bytes of keys and ranks per particle -- against order^3 times the NGP workspace and 12 + 4 C bytes of expanded arrays per
+ * sub-particle.  Timers: the sort under VPS_K_DEPOSIT, the accumulation under VPS_K_ALGEBRA, as in the NGP route. */
+size_t vps_deposit_assign_workspace_bytes(int64_t np, int C, int N, int order);
+int vps_deposit_assign(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* payload_dev, int64_t np, int C, int N,
+                       double Lbox, int order, float* grid_dev, void* work_dev);
+/* What vps_deposit_assign WOULD do (a pure host-side query like vps_deposit_plan).  out[] =
+ *   0 bx, 1 by, 2 bz       cells of one brick per axis;  3 nbx, 4 nby, 5 nbz  bricks per axis (the last may be partial)
+ *   6 nbuckets, 7 cells    bricks of the grid, cells per brick
+ *   8 two_level            1: two-level sort, 0: one returning atomic per particle (option sort_atomic, or a geometry the
+ *                          two-level sort does not cover)
+ *   9 wide_keys            64-bit keys: nbuckets * cells does not fit 32 bits
+ *   10 record_words        32-bit words of a record (C + 7)
+ *   11 staged, 12 gshift   level-1 scatter staged in LDS; level-1 groups of 2^gshift buckets
+ *   13 max_sources         the most source buckets any brick gathers from.
+ * Tests aim particles with it. */
+#define VPS_DEPOSIT_ASSIGN_PLAN_FIELDS 14
+int vps_deposit_assign_plan(vps_ctx* ctx, int64_t np, int C, int N, int order, int64_t out[VPS_DEPOSIT_ASSIGN_PLAN_FIELDS]);
 
 /* out_dev[np][4] = [vx*rho, vy*rho, vz*rho, rho]: GasParticles.density_velocity_vector
  * (vpower/interp.py:199-213).  vel_dev [np][3], rho_dev [np], float32.             */

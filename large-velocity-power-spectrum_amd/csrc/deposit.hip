@@ -1017,6 +1017,384 @@ int check_deposit_args(vps_ctx* ctx, const char* who, int64_t np, int N, double 
   return VPS_OK;
 }
 
+// ---- direct CIC / TSC deposit: one record per PARTICLE, owner-computes accumulation --------------------------------------
+// The expansion above moves 8 / 27 records per particle through the sort.  Here a particle is sorted ONCE, into the brick of its
+// base cell c0 (the lowest cell it touches on each axis), with a record {cell-in-brick, payload[C], 6 weight words}; the brick
+// that OWNS a grid cell then gathers: it walks its own bucket and the buckets of the bricks that hold the order - 1 cells below
+// its range on every axis (usually the -1 neighbour: at most 8 buckets), and adds payload * wx * wy * wz into its LDS tile for
+// every (record, offset) whose target cell (c0 + j) mod N lies in its own range.  Every (particle, offset) pair has exactly one
+// owner, so it is counted exactly once; every grid cell is written exactly once, by plain streaming stores, as in the NGP route:
+// no grid memset, no global float atomic.  Whole grid only (x0 = 0, nx = N): a slab would need the particles of its lower
+// neighbour's last cells, which the expansion route gets for free from replicated particles.
+//
+// c0 is the float64 rule of assign_expand_kernel -- s = (double)pos / lcell, floor(s - 1/2) for CIC, floor(s) - 1 for TSC,
+// wrapped into [0, N) BEFORE the conversion to int (wrap_cell's expression) -- never cell_of<F>, the NGP rule in the particle's
+// dtype, which can differ by a cell at a face: the particle would then sit in a bucket its targets' owners do not read.
+// A position whose s is not finite (NaN, inf), or so large (beyond 2^53 cells) that the wrapped cell number does not come out in
+// [0, N), gets sort_invalid and is SKIPPED: it deposits nowhere.  (The expansion route makes no promise for such positions.)
+template <int ORDER>
+__device__ __forceinline__ double assign_base_cell(double s) {
+  return ORDER == 2 ? floor(s - 0.5) : floor(s) - 1.0;
+}
+
+template <typename F, typename K, int ORDER>
+struct AssignKeyOf {
+  const F* __restrict__ pos;
+  double lcell, n;
+  Bricks b;
+  __device__ __forceinline__ K operator()(long long i) const {
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double f0 = assign_base_cell<ORDER>((double)pos[i * 3 + a] / lcell);
+      const double r = f0 - floor(f0 / n) * n;          // wrap_cell, before its conversion
+      if (!(r >= 0.0 && r < n)) return sort_invalid<K>();   // NaN, inf, beyond 2^53
+      c[a] = (int)r;
+    }
+    const int ix = c[0] / b.bx, iy = c[1] / b.by, iz = c[2] / b.bz;
+    const unsigned brick = (unsigned)((ix * b.nby + iy) * b.nbz + iz);
+    const unsigned loc = (unsigned)(((c[0] - ix * b.bx) * b.by + (c[1] - iy * b.by)) * b.bz + (c[2] - iz * b.bz));
+    return (K)brick * (unsigned)b.cells + loc;
+  }
+};
+
+// payload[C] and, per axis, TWO float32 numbers each rounded once from float64, so that a small weight keeps its relative
+// precision (a weight of 1e-9 next to a cell centre would lose all of it if 1 - f were formed in float32 from a rounded f):
+//   CIC: (float)(1 - f), (float)f                         -- the two weights themselves
+//   TSC: a = (float)(1/2 - d), b = (float)(1/2 + d)       -- weights a a / 2, 1/2 + a b (= 3/4 - d^2), b b / 2 (assign_axis_weights)
+template <typename F, int CP, int ORDER>
+struct AssignPayload {
+  static constexpr int C = CP + 6;
+  const F* __restrict__ pos;
+  const float* __restrict__ payload;
+  double lcell;
+  __device__ __forceinline__ void load(long long i, float val[CP + 6]) const {
+    load_payload<CP, false>(payload, nullptr, i, val);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double s = (double)pos[i * 3 + a] / lcell;
+      if constexpr (ORDER == 2) {
+        const double f = s - 0.5 - floor(s - 0.5);
+        val[CP + 2 * a] = (float)(1.0 - f);
+        val[CP + 2 * a + 1] = (float)f;
+      } else {
+        const double d = s - (floor(s) + 0.5);
+        val[CP + 2 * a] = (float)(0.5 - d);
+        val[CP + 2 * a + 1] = (float)(0.5 + d);
+      }
+    }
+  }
+};
+
+template <int ORDER>
+__device__ __forceinline__ void assign_axis_weights(float a, float b, float w[ORDER]) {
+  if constexpr (ORDER == 2) {
+    w[0] = a;
+    w[1] = b;
+  } else {
+    w[0] = 0.5f * (a * a);
+    w[1] = 0.5f + a * b;
+    w[2] = 0.5f * (b * b);
+  }
+}
+
+// The bricks along one axis whose buckets brick i gathers from: itself, then the bricks holding the cells lo - 1 .. lo - (order - 1)
+// (periodic), distinct.  With one brick on the axis that is the brick itself, with two the -1 and the +1 neighbour are the same
+// brick, and where the last, partial brick is narrower than order - 1 cells (one cell at N = 65, TSC) brick 0 also reads the one
+// before it: the set is formed from the cells, so no grid needs refusing.  Returns the count (<= 3).
+__host__ __device__ inline int assign_axis_sources(int i, int bw, int N, int order, int src[3]) {
+  int n = 0;
+  src[n++] = i;
+  const int lo = i * bw;
+  for (int k = 1; k < order; ++k) {
+    const int cell = ((lo - k) % N + N) % N;
+    const int s = cell / bw;
+    bool seen = false;
+    for (int m = 0; m < n; ++m) seen = seen || src[m] == s;
+    if (!seen) src[n++] = s;
+  }
+  return n;
+}
+
+// one-atomic-per-particle ranking with the key of any functor (option sort_atomic, or a geometry the two-level sort does not
+// cover): what brick_rank_kernel / brick_scatter_kernel do for the NGP key and payload
+template <typename KeyOf>
+__global__ void __launch_bounds__(256)
+    assign_rank_kernel(KeyOf key_of, long long np, unsigned cells, unsigned* __restrict__ count,
+                       unsigned long long* __restrict__ keys, unsigned* __restrict__ ranks) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  const unsigned long long key = key_of(i);
+  keys[i] = key;
+  if (key != ~0ull) ranks[i] = atomicAdd(&count[key / cells], 1u);
+}
+
+template <typename Payload>
+__global__ void __launch_bounds__(256)
+    assign_scatter_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ ranks, Payload pay,
+                          long long np, unsigned cells, const unsigned* __restrict__ start, unsigned* __restrict__ records) {
+  constexpr int C = Payload::C;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  const unsigned long long key = keys[i];
+  if (key == ~0ull) return;
+  float val[C];
+  pay.load(i, val);
+  unsigned* rec = records + (size_t)(start[key / cells] + ranks[i]) * (C + 1);
+  rec[0] = (unsigned)(key % cells);
+#pragma unroll
+  for (int c = 0; c < C; ++c) rec[1 + c] = __float_as_uint(val[c]);
+}
+
+// records {cell-in-brick of c0, payload[C], 6 weight words} grouped by the brick of c0 -> grid [C][N][N][N], every cell written
+template <int C, int ORDER>
+__global__ void __launch_bounds__(256)
+    assign_accumulate_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start, Bricks b,
+                             long long nbricks, float* __restrict__ grid) {
+  constexpr int W = C + 7;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* tile = reinterpret_cast<float*>(smem_raw);  // [C][cells]
+  const int cells = b.cells, N = b.N;
+  const bool vec4 = ((b.bz & 3) == 0) && ((N & 3) == 0);
+  for (int i = threadIdx.x; i < C * cells; i += blockDim.x) tile[i] = 0.f;
+  const long long plane = (long long)N * N * N;
+  __syncthreads();
+  for (long long brick = blockIdx.x; brick < nbricks; brick += gridDim.x) {
+    const int iz = (int)(brick % b.nbz), iy = (int)((brick / b.nbz) % b.nby);
+    const int ix = (int)(brick / ((long long)b.nbz * b.nby));
+    const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
+    // the cells this brick owns: [g0, g1) per axis (the last brick of an axis may be partial)
+    const int gx1 = min(gx0 + b.bx, N), gy1 = min(gy0 + b.by, N), gz1 = min(gz0 + b.bz, N);
+    int srcx[3], srcy[3], srcz[3];
+    const int nsx = assign_axis_sources(ix, b.bx, N, ORDER, srcx);
+    const int nsy = assign_axis_sources(iy, b.by, N, ORDER, srcy);
+    const int nsz = assign_axis_sources(iz, b.bz, N, ORDER, srcz);
+    for (int sx = 0; sx < nsx; ++sx)
+      for (int sy = 0; sy < nsy; ++sy)
+        for (int sz = 0; sz < nsz; ++sz) {
+          const long long sb = ((long long)srcx[sx] * b.nby + srcy[sy]) * b.nbz + srcz[sz];
+          const unsigned s = start[sb], e = start[sb + 1];
+          const int ox = srcx[sx] * b.bx, oy = srcy[sy] * b.by, oz = srcz[sz] * b.bz;     // first cell of the source brick
+          for (unsigned j = s + threadIdx.x; j < e; j += blockDim.x) {
+            const unsigned* rec = records + (size_t)j * W;
+            const int loc = (int)rec[0];
+            int lz, ly, lx;
+            if (b.pow2) {
+              lz = loc & (b.bz - 1);
+              ly = (loc >> b.sz) & (b.by - 1);
+              lx = loc >> (b.sz + b.sy);
+            } else {
+              lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
+            }
+            // target cells per axis, relative to this brick; a record none of whose targets on some axis is ours is dropped
+            // before its payload and weights are read (most records of a neighbour's bucket)
+            int tx[ORDER], ty[ORDER], tz[ORDER];
+            bool anyx = false, anyy = false, anyz = false;
+#pragma unroll
+            for (int k = 0; k < ORDER; ++k) {
+              int t = ox + lx + k;
+              if (t >= N) t %= N;
+              tx[k] = (t >= gx0 && t < gx1) ? t - gx0 : -1;
+              anyx = anyx || tx[k] >= 0;
+              t = oy + ly + k;
+              if (t >= N) t %= N;
+              ty[k] = (t >= gy0 && t < gy1) ? t - gy0 : -1;
+              anyy = anyy || ty[k] >= 0;
+              t = oz + lz + k;
+              if (t >= N) t %= N;
+              tz[k] = (t >= gz0 && t < gz1) ? t - gz0 : -1;
+              anyz = anyz || tz[k] >= 0;
+            }
+            if (!(anyx && anyy && anyz)) continue;
+            float pay[C], wx[ORDER], wy[ORDER], wz[ORDER];
+#pragma unroll
+            for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
+            assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
+            assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
+            assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
+#pragma unroll
+            for (int kx = 0; kx < ORDER; ++kx) {
+              if (tx[kx] < 0) continue;
+#pragma unroll
+              for (int ky = 0; ky < ORDER; ++ky) {
+                if (ty[ky] < 0) continue;
+#pragma unroll
+                for (int kz = 0; kz < ORDER; ++kz) {
+                  if (tz[kz] < 0) continue;
+                  const float wt = wx[kx] * wy[ky] * wz[kz];      // (the product order of assign_expand_kernel)
+                  const int at = (tx[kx] * b.by + ty[ky]) * b.bz + tz[kz];
+#pragma unroll
+                  for (int c = 0; c < C; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
+                }
+              }
+            }
+          }
+        }
+    __syncthreads();
+    // stream the tile out (rows of bz cells are contiguous in the grid) and zero it for the next brick
+    if (vec4) {
+      typedef float vf4 __attribute__((ext_vector_type(4)));
+      for (int i = threadIdx.x; i < cells / 4; i += blockDim.x) {
+        const int loc = i * 4;
+        int lz, ly, lx;
+        if (b.pow2) {
+          lz = loc & (b.bz - 1);
+          ly = (loc >> b.sz) & (b.by - 1);
+          lx = loc >> (b.sz + b.sy);
+        } else {
+          lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
+        }
+        const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
+        const bool inside = gx < N && gy < N && gz < N;      // (N and bz multiples of 4: a quad is inside or outside as a whole)
+        const long long cell = ((long long)gx * N + gy) * N + gz;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          float4* t = reinterpret_cast<float4*>(tile + c * cells + loc);
+          const float4 val = *t;
+          *t = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (inside) {
+            vf4 q; q.x = val.x; q.y = val.y; q.z = val.z; q.w = val.w;
+            __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(grid + c * plane + cell));
+          }
+        }
+      }
+    } else {
+      for (int loc = threadIdx.x; loc < cells; loc += blockDim.x) {
+        const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
+        const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
+        const bool inside = gx < N && gy < N && gz < N;
+        const long long cell = ((long long)gx * N + gy) * N + gz;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const float v = tile[c * cells + loc];
+          tile[c * cells + loc] = 0.f;
+          if (inside) __builtin_nontemporal_store(v, grid + c * plane + cell);
+        }
+      }
+    }
+    __syncthreads();   // tile is all zero again
+  }
+}
+
+// brick geometry and sort layout of the direct route: the bricks of the NGP deposit of C channels (the LDS tile holds the C
+// payload channels only), records of C + 6 channels
+struct AssignPlan {
+  Bricks b;
+  DepLayout l;
+};
+AssignPlan assign_plan(int64_t np, int C, int N) {
+  AssignPlan p;
+  p.b = make_bricks(N, 0, N, C);
+  p.l = dep_layout(np, C + 6, p.b);
+  return p;
+}
+
+int check_assign_args(vps_ctx* ctx, const char* who, int64_t np, int C, int N, int order) {
+  if (np < 0 || N < 1) return vps_fail(ctx, VPS_ERR_ARG, "%s: bad np/N", who);
+  if (order != 2 && order != 3) return vps_fail(ctx, VPS_ERR_ARG, "%s: order must be 2 (CIC) or 3 (TSC)", who);
+  if (C != 1 && C != 3 && C != 4) return vps_fail(ctx, VPS_ERR_ARG, "%s: C=%d channels (supported: 1,3,4)", who, C);
+  if ((np + 255) / 256 > 0x7fffffffLL) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "%s: np too large for one launch", who);
+  if (np > 0xffffffffLL) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "%s: np exceeds 32-bit bucket offsets", who);
+  return VPS_OK;
+}
+
+// particles -> records grouped by the brick of c0 + start[]: sort_into_buckets with the key and payload of the direct route
+template <typename F, int C, int ORDER>
+int assign_sort(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, double lcell, const AssignPlan& p, char* work) {
+  constexpr int CR = C + 6;
+  typedef AssignPayload<F, C, ORDER> Pay;
+  const Bricks& b = p.b;
+  const DepLayout& l = p.l;
+  unsigned* count = reinterpret_cast<unsigned*>(work + l.count);
+  unsigned* start = reinterpret_cast<unsigned*>(work + l.start);
+  unsigned* records = reinterpret_cast<unsigned*>(work + l.records);
+  const Pay pay{pos, payload, lcell};
+  vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
+  if (np == 0) {
+    VPS_HIP_CHECK(ctx, hipMemsetAsync(start, 0, sizeof(unsigned) * (l.nbricks + 1), ctx->stream));
+    return VPS_OK;
+  }
+  if (l.two_level) {
+    const SortGeom& g = l.geom;
+    unsigned* table = reinterpret_cast<unsigned*>(work + l.table);
+    unsigned* table_start = reinterpret_cast<unsigned*>(work + l.table_start);
+    unsigned* table_tiles = reinterpret_cast<unsigned*>(work + l.table_tiles);
+    unsigned* rec1 = reinterpret_cast<unsigned*>(work + l.rec1);
+    const size_t lds1 = sort_hist_lds(g), lds2 = sort_fine_lds(g);
+    const size_t lds_staged = sort_staged_lds(g, CR, SORT_ITEMS);
+    const bool staged = sort_staged() && lds_staged <= ctx->lds_per_cu;
+    auto level1 = [&](auto* keys) -> int {
+      typedef typename std::remove_pointer<decltype(keys)>::type K;
+      typedef AssignKeyOf<F, K, ORDER> Key;
+      hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, Key>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
+                         Key{pos, lcell, (double)b.N, b}, (long long)np, g, keys, table);
+      launch_exclusive_scan(ctx->stream, table, (long long)g.ngroups * g.nchunks, table_tiles, table_start);
+      if (staged) {
+        auto kern = sort_scatter_staged_kernel<SORT_ITEMS, K, Pay>;
+        if (lds_staged > 64 * 1024)
+          VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds_staged));
+        hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((g.nchunks + 7) / 8))), dim3(SORT_THREADS), lds_staged, ctx->stream,
+                           (const K*)keys, pay, (long long)np, g, table_start, rec1);
+      } else {
+        hipLaunchKernelGGL((sort_scatter_kernel<SORT_ITEMS, K, Pay>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
+                           (const K*)keys, pay, (long long)np, g, table_start, rec1);
+      }
+      return VPS_OK;
+    };
+    const int rc1 = l.wide_keys ? level1(reinterpret_cast<unsigned long long*>(work + l.keys))
+                                : level1(reinterpret_cast<unsigned*>(work + l.keys));
+    if (rc1) return rc1;
+    hipLaunchKernelGGL((sort_fine_kernel<CR, true>), dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1, g,
+                       table_start, start, records);
+  } else {
+    typedef AssignKeyOf<F, unsigned long long, ORDER> Key;
+    unsigned* tiles = reinterpret_cast<unsigned*>(work + l.tiles);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(work + l.keys);
+    unsigned* ranks = reinterpret_cast<unsigned*>(work + l.ranks);
+    VPS_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(unsigned) * l.nbricks, ctx->stream));
+    const unsigned pblocks = (unsigned)((np + 255) / 256);
+    hipLaunchKernelGGL(assign_rank_kernel<Key>, dim3(pblocks), dim3(256), 0, ctx->stream, Key{pos, lcell, (double)b.N, b},
+                       (long long)np, (unsigned)b.cells, count, keys, ranks);
+    launch_exclusive_scan(ctx->stream, count, l.nbricks, tiles, start);
+    hipLaunchKernelGGL(assign_scatter_kernel<Pay>, dim3(pblocks), dim3(256), 0, ctx->stream, keys, ranks, pay, (long long)np,
+                       (unsigned)b.cells, start, records);
+  }
+  VPS_HIP_CHECK(ctx, hipGetLastError());
+  return VPS_OK;
+}
+
+template <typename F, int C, int ORDER>
+int deposit_assign_run(vps_ctx* ctx, const void* pos_v, const float* payload, int64_t np, int N, double Lbox, float* grid,
+                       void* work_v) {
+  const AssignPlan p = assign_plan(np, C, N);
+  char* work = reinterpret_cast<char*>(work_v);
+  const double lcell = Lbox / (double)N;      // float64 whatever the dtype of pos (assign_expand_kernel's)
+  const int rc = assign_sort<F, C, ORDER>(ctx, reinterpret_cast<const F*>(pos_v), payload, np, lcell, p, work);
+  if (rc) return rc;
+  {
+    vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
+    const size_t lds = (size_t)C * p.b.cells * sizeof(float);
+    long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    long long grid_wg = (long long)ctx->num_cu * per_cu;
+    if (grid_wg > p.l.nbricks) grid_wg = p.l.nbricks;
+    hipLaunchKernelGGL((assign_accumulate_kernel<C, ORDER>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+                       reinterpret_cast<const unsigned*>(work + p.l.records), reinterpret_cast<const unsigned*>(work + p.l.start),
+                       p.b, p.l.nbricks, grid);
+  }
+  VPS_HIP_CHECK(ctx, hipGetLastError());
+  return VPS_OK;
+}
+
+template <typename F, int C>
+int deposit_assign_order(vps_ctx* ctx, const void* pos, const float* payload, int64_t np, int N, double Lbox, int order,
+                         float* grid, void* work) {
+  return order == 2 ? deposit_assign_run<F, C, 2>(ctx, pos, payload, np, N, Lbox, grid, work)
+                    : deposit_assign_run<F, C, 3>(ctx, pos, payload, np, N, Lbox, grid, work);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1311,6 +1689,59 @@ int vps_assign_expand(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
                          order, pos_out_dev, payload_out_dev);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
+  return VPS_OK;
+}
+
+size_t vps_deposit_assign_workspace_bytes(int64_t np, int C, int N, int order) {
+  if (np < 0 || N < 1 || (C != 1 && C != 3 && C != 4) || (order != 2 && order != 3)) return 0;
+  return assign_plan(np, C, N).l.total;
+}
+
+int vps_deposit_assign(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* payload_dev, int64_t np, int C, int N,
+                       double Lbox, int order, float* grid_dev, void* work_dev) {
+  VPS_ENTER(ctx);
+  int rc = check_assign_args(ctx, "vps_deposit_assign", np, C, N, order);
+  if (rc) return rc;
+  if (!(Lbox > 0)) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_assign: bad Lbox");
+  if (!grid_dev || !work_dev || (np > 0 && (!pos_dev || !payload_dev)))
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_assign: null buffer");
+#define VPS_DEP(CC)                                                                                              \
+  (pos_is_f64 ? deposit_assign_order<double, CC>(ctx, pos_dev, payload_dev, np, N, Lbox, order, grid_dev, work_dev) \
+              : deposit_assign_order<float, CC>(ctx, pos_dev, payload_dev, np, N, Lbox, order, grid_dev, work_dev))
+  switch (C) {
+    case 1: return VPS_DEP(1);
+    case 3: return VPS_DEP(3);
+    default: return VPS_DEP(4);
+  }
+#undef VPS_DEP
+}
+
+int vps_deposit_assign_plan(vps_ctx* ctx, int64_t np, int C, int N, int order, int64_t out[VPS_DEPOSIT_ASSIGN_PLAN_FIELDS]) {
+  if (!ctx) return VPS_ERR_ARG;
+  if (!out) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_assign_plan: null buffer");
+  int rc = check_assign_args(ctx, "vps_deposit_assign_plan", np, C, N, order);
+  if (rc) return rc;
+  const AssignPlan p = assign_plan(np, C, N);
+  const Bricks& b = p.b;
+  const size_t lds_staged = sort_staged_lds(p.l.geom, C + 6, SORT_ITEMS);
+  // the largest set of source buckets any brick gathers from (8 unless a partial last brick is narrower than order - 1 cells)
+  int most[3] = {1, 1, 1};
+  const int bw[3] = {b.bx, b.by, b.bz}, nb[3] = {b.nbx, b.nby, b.nbz};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; i < nb[a]; ++i) {
+      int src[3];
+      most[a] = std::max(most[a], assign_axis_sources(i, bw[a], N, order, src));
+    }
+  out[0] = b.bx; out[1] = b.by; out[2] = b.bz;
+  out[3] = b.nbx; out[4] = b.nby; out[5] = b.nbz;
+  out[6] = p.l.nbricks;
+  out[7] = b.cells;
+  out[8] = p.l.two_level;
+  out[9] = p.l.wide_keys;
+  out[10] = C + 7;
+  out[11] = p.l.two_level && sort_staged() && lds_staged <= ctx->lds_per_cu;   // (assign_sort's rule)
+  out[12] = p.l.geom.gshift;
+  out[13] = (int64_t)most[0] * most[1] * most[2];
   return VPS_OK;
 }
 

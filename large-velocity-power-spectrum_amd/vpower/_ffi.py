@@ -73,6 +73,9 @@ SYMBOLS = (
     ("vps_set_window", C.c_int, (_vp, C.c_int, _vp)),
     ("vps_set_density_weight", C.c_int, (_vp, C.c_double)),
     ("vps_assign_expand", C.c_int, (_vp, _vp, C.c_int, _vp, _i64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp)),
+    ("vps_deposit_assign_workspace_bytes", C.c_size_t, (_i64, C.c_int, C.c_int, C.c_int)),
+    ("vps_deposit_assign", C.c_int, (_vp, _vp, C.c_int, _vp, _i64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp)),
+    ("vps_deposit_assign_plan", C.c_int, (_vp, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(_i64))),
     ("vps_fft_workspace_bytes", C.c_size_t, (C.c_int, C.c_int)),
     ("vps_fft_zy", C.c_int, (_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp)),
     ("vps_fft_zy_weighted", C.c_int, (_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp)),
@@ -123,10 +126,12 @@ KERNEL_KINDS = {"deposit": K_DEPOSIT, "algebra": K_ALGEBRA, "fft_z": K_FFT_Z, "f
 
 DEPOSIT_PLAN_FIELDS = ("bx", "by", "bz", "nbuckets", "cells", "cells_pow2", "two_level", "wide_keys", "gshift", "ngroups", "nchunks",
                        "staged", "staged_lds", "recompute", "cap_in")   # include/vps_hip.h: vps_deposit_plan
+DEPOSIT_ASSIGN_PLAN_FIELDS = ("bx", "by", "bz", "nbx", "nby", "nbz", "nbuckets", "cells", "two_level", "wide_keys", "record_words",
+                              "staged", "gshift", "max_sources")   # include/vps_hip.h: vps_deposit_assign_plan
 NN_PLAN_FIELDS = ("M", "ncell", "sorted", "gshift", "ngroups", "nchunks", "lds_scatter", "lds_fine")   # include/vps_hip.h: vps_nn_plan
 NN_SEARCH_KINDS = ("ring", "scatter", "column")          # include/vps_hip.h: VPS_NN_SEARCH_*
 NN_LAST_SEARCH_FIELDS = ("kind", "tiles", "radii", "open")   # include/vps_hip.h: vps_nn_last_search
-ABI_VERSION = 12  # include/vps_hip.h: VPS_ABI_VERSION
+ABI_VERSION = 13  # include/vps_hip.h: VPS_ABI_VERSION
 FFT_PARTS = 4   # fft_parts.hip (the FFT's kernels) is compiled once per family of line lengths (-DVPS_FFT_PART=k)
 
 

@@ -630,6 +630,29 @@ class HipKernels:
                                              n, C_, int(N), float(Lbox), order, self._ptr(pos_o), self._ptr(pay_o)))
         return pos_o, pay_o
 
+    def deposit_assign(self, pos, payload, N, Lbox, assignment, out=None):
+        """CIC / TSC without the expansion (vps_deposit_assign): (pos [np,3], payload [np,C] float32, C in 1, 3, 4) -> the whole
+        grid [C, N, N, N] float32, every cell written; one sort record per particle, each brick gathers from its own and its
+        lower neighbours' buckets.  `assignment` = "ngp" is `deposit` on the whole grid."""
+        order = ASSIGNMENT_ORDER[assignment]
+        if order == 1:
+            return self.deposit(pos, payload, N, Lbox, 0, N, out=out)
+        self._stream()
+        n, C_ = payload.shape
+        if out is None:
+            out = self.empty((C_, N, N, N), torch.float32)
+        work = self.workspace("deposit_assign", self.lib.vps_deposit_assign_workspace_bytes(n, C_, int(N), order))
+        self._chk(self.lib.vps_deposit_assign(self.ctx, self._ptr(pos), self._pos_kind(pos), self._ptr(payload, torch.float32),
+                                              n, C_, int(N), float(Lbox), order, self._ptr(out, torch.float32), self._ptr(work)))
+        return out
+
+    def deposit_assign_plan(self, np_, C_, N, assignment):
+        """Brick geometry and sort path of deposit_assign for np_ particles with C_ channels under the current options
+        (vps_deposit_assign_plan; nothing runs): {field: int} over _ffi.DEPOSIT_ASSIGN_PLAN_FIELDS."""
+        out = (C.c_int64 * len(_ffi.DEPOSIT_ASSIGN_PLAN_FIELDS))()
+        self._chk(self.lib.vps_deposit_assign_plan(self.ctx, int(np_), int(C_), int(N), ASSIGNMENT_ORDER[assignment], out))
+        return dict(zip(_ffi.DEPOSIT_ASSIGN_PLAN_FIELDS, (int(v) for v in out)))
+
     def fft_zy(self, field, N, nx, spec=None, nyq=None, weight=None):
         """field [nx,N,N] float32 (times `weight`, same shape, if given) -> spec [N/2,N,nx], nyq [N,nx] (complex64)."""
         self._stream()

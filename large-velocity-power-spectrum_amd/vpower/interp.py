@@ -220,20 +220,27 @@ class GasParticles:
         # straight into the fields of q (vps_nn_resample_quantity: no mass channel written, no weighted z pass).
         return BoxField._from_neighbours((self._device_pos(k), self._device_payload(k), ax), Nsize, Lcell)
 
-    def deposit_to_field(self, Nsize, assignment="ngp"):
+    def deposit_to_field(self, Nsize, assignment="ngp", method="expand"):
         """NGP composition the reference leaves to the caller: deposit_to_grid of
         density_velocity_vector (interp.py:996-1015), then v=rho v/rho with empty cells set
         to 0 (the rule of interp.py:329-331) and m=rho*Lcell^3 (interp.py:272-273).
         `assignment` = "cic" / "tsc" (extension; the reference offers NGP, NN and Voxelize) spreads
         [rho v, rho] over 8 / 27 cells; `BoxField.spctrm(..., deconvolve=True)` then divides the
-        spectrum by the assignment window."""
+        spectrum by the assignment window.  `method` says how: "expand" writes every particle out as 8 / 27
+        weighted sub-particles for the NGP deposit, "direct" sorts one record per particle and lets every
+        brick gather from its neighbours (the same grid up to float32 summation order, an order^3-th of the
+        sort and the workspace); with "ngp" both are the NGP route."""
+        _check_method(method)
         k = _kernels()
         vel, rho = self._device_vel(k), self._device_rho(k)
         if assignment != "ngp":
             if assignment not in _dev.ASSIGNMENT_ORDER:
                 raise Exception("assignment must be 'ngp', 'cic' or 'tsc'")
-            pos_e, pay_e = k.assign_expand(self._device_pos(k), self._device_payload(k), Nsize, self.Lbox, assignment)
-            grid = k.deposit(pos_e, pay_e, Nsize, self.Lbox, 0, Nsize)
+            if method == "direct":
+                grid = k.deposit_assign(self._device_pos(k), self._device_payload(k), Nsize, self.Lbox, assignment)
+            else:
+                pos_e, pay_e = k.assign_expand(self._device_pos(k), self._device_payload(k), Nsize, self.Lbox, assignment)
+                grid = k.deposit(pos_e, pay_e, Nsize, self.Lbox, 0, Nsize)
             k.field_algebra(grid, _dev.VM, 0, self.Lbox / Nsize)
             box = BoxField._from_device(grid, self.Lbox / Nsize)
             box.assignment = assignment
@@ -553,10 +560,21 @@ def check_conservation(gasParticles, boxField) -> tuple:
 # --------------------------------------------------------------------------- #
 # free functions
 # --------------------------------------------------------------------------- #
-def deposit_to_grid(f, pos, Nsize, Lbox, assignment="ngp"):
+METHODS = ("expand", "direct")
+
+
+def _check_method(method):
+    """The `method=` of the higher-order assignments; checked before anything touches the device."""
+    if method not in METHODS:
+        raise ValueError("method must be 'expand' or 'direct', not %r" % (method,))
+
+
+def deposit_to_grid(f, pos, Nsize, Lbox, assignment="ngp", method="expand"):
     """Nearest-grid-point scatter-add of f (Np,) or (Np,C) into an (N,N,N[,C]) float64 grid;
     cell = int((pos // Lcell) % Nsize), periodic (interp.py:996-1015).  `assignment` = "cic" / "tsc"
-    (extension) spreads every particle over 8 / 27 cells."""
+    (extension) spreads every particle over 8 / 27 cells: `method` = "expand" as weighted sub-particles through
+    the NGP deposit, "direct" with one sort record per particle (GasParticles.deposit_to_field)."""
+    _check_method(method)
     k = _kernels()
     f = np.asarray(f)
     f2 = f[:, None] if f.ndim == 1 else f
@@ -567,8 +585,11 @@ def deposit_to_grid(f, pos, Nsize, Lbox, assignment="ngp"):
     c = 0
     while c < f2.shape[1]:      # the kernel takes 1, 3 or 4 channels per launch
         w = 4 if f2.shape[1] - c >= 4 else (3 if f2.shape[1] - c == 3 else 1)
-        pe, fe = k.assign_expand(post, k.to_device(f2[:, c:c + w], torch.float32), Nsize, Lbox, assignment)
-        g = k.deposit(pe, fe, Nsize, Lbox, 0, Nsize)
+        if method == "direct":
+            g = k.deposit_assign(post, k.to_device(f2[:, c:c + w], torch.float32), Nsize, Lbox, assignment)
+        else:
+            pe, fe = k.assign_expand(post, k.to_device(f2[:, c:c + w], torch.float32), Nsize, Lbox, assignment)
+            g = k.deposit(pe, fe, Nsize, Lbox, 0, Nsize)
         cols.append(g)
         c += w
     grid = torch.cat(cols, dim=0).permute(1, 2, 3, 0).cpu().numpy().astype(np.float64)
