@@ -14,8 +14,42 @@
  *     negative vps_status; nothing throws.  vps_last_error() gives the message.
  *   - "dev" pointers are device (HBM) addresses owned by the CALLER (e.g.
  *     torch.Tensor.data_ptr() or vps_malloc); "host" pointers are ordinary memory.
- *   - All work is enqueued on the context's stream (vps_set_stream; default: the
- *     null stream); only vps_sync, vps_timing_get, vps_memcpy_d2h block.
+ *   - Streams.  All device work is enqueued on the context's stream (vps_set_stream;
+ *     default: the null stream), the library's own memsets, copies and table uploads
+ *     included; tests/stream_probe.py lists every entry point under one of three heads.
+ *       PURE ENQUEUES return while the stream may still be busy: vps_memset,
+ *         vps_cell_index, vps_density_velocity_vector, vps_deposit_ngp, vps_deposit_field,
+ *         vps_deposit_fft_zy, vps_deposit_fft_z, vps_assign_expand, vps_deposit_assign,
+ *         vps_field_algebra[_out], vps_fft_zy[_weighted], vps_fft_z, vps_fft_y, vps_fft_x,
+ *         vps_fft_x_bin[_chunk][_helmholtz], vps_power_bin, vps_rfft3, vps_power_grid,
+ *         vps_spectrum_zimages, vps_allreduce_shells, vps_set_stream.  One exception: a
+ *         call that must regrow or rebuild a table the CONTEXT owns (the x pass's partial
+ *         sums, the chunk tables of vps_fft_y after new binning tables or another chunk
+ *         count, FFT twiddles of a new length) drains the stream first, that once.
+ *       BLOCKING calls return only after the stream has drained, each because it brings a
+ *         value to the host: vps_preprocess (minimum, bulk velocity), vps_totals,
+ *         vps_count_in_slab, vps_deposit_fft_z_slab (the compaction counter of a slab-sized
+ *         sort), vps_nn_resample* (bounding box; open-point count under timing),
+ *         vps_hist_pairs, vps_memcpy_d2h, vps_timing_reset / _get / _list, vps_sync,
+ *         vps_destroy, vps_comm_destroy; vps_set_binning and vps_set_window when the table
+ *         CHANGES (a pending launch may still read the old one; unchanged tables: nothing
+ *         happens); vps_pair_k and vps_memcpy_h2d take host data in stream order and
+ *         complete the copy before returning.
+ *       Everything else is host-only: nothing is enqueued.
+ *     HOST POINTERS ARE FREE ON RETURN of every call, and the library enforces it: tables
+ *     and edges go up by a synchronous copy, pointer lists are read on the host, and every
+ *     call that copies host axes in stream order drains the stream behind the copy; no
+ *     call relies on how the runtime treats pageable memory.
+ *     vps_set_stream with ANOTHER stream than the current one records an event on the old
+ *     stream and makes the new one wait for it: what earlier calls left for later ones --
+ *     the context's tables and partial sums, the caller's sort workspace under
+ *     VPS_FLAG_REUSE_SORT / VPS_FLAG_SHARE_ENERGY -- is complete before the first call on
+ *     the new stream reads it.  The old stream must still exist at that moment: if it was
+ *     destroyed first the call reports VPS_ERR_HIP once, nothing is ordered behind it, and
+ *     the context is on the new stream all the same.  The event is recorded on the old
+ *     stream, which ends a stream capture in progress there (the library captures none).
+ *     With the same stream it does nothing (one pointer compare).  Buffers the CALLER hands from
+ *     one stream to another are the caller's to order, as with any stream-ordered library.
  *   - Grids are float32, C order.  A multi-channel grid is channel-major (SoA):
  *     grid[c][x][y][z].  Slab decomposition is along x: a rank owns
  *     x in [x0, x0+nx).  N is the global cells-per-axis.
@@ -134,7 +168,7 @@ int vps_set_density_weight(vps_ctx* ctx, double alpha);
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);
 int vps_free(vps_ctx* ctx, void* dev);
 int vps_memset(vps_ctx* ctx, void* dev, int value, size_t bytes);
-int vps_memcpy_h2d(vps_ctx* ctx, void* dev, const void* host, size_t bytes);
+int vps_memcpy_h2d(vps_ctx* ctx, void* dev, const void* host, size_t bytes); /* blocks */
 int vps_memcpy_d2h(vps_ctx* ctx, void* host, const void* dev, size_t bytes); /* blocks */
 
 /* ---- per-kernel timing (HIP events on the context's stream) -------------- */

@@ -146,6 +146,7 @@ int vps_destroy(vps_ctx* ctx) {
     (void)hipEventDestroy(l.stop);
   }
   for (auto& e : ctx->event_pool) (void)hipEventDestroy(e);
+  if (ctx->ev_switch) (void)hipEventDestroy(ctx->ev_switch);
   delete ctx;
   return VPS_OK;
 }
@@ -154,7 +155,19 @@ const char* vps_last_error(const vps_ctx* ctx) { return ctx ? ctx->err : g_last_
 
 int vps_set_stream(vps_ctx* ctx, void* hip_stream) {
   VPS_ENTER(ctx);
-  ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
+  hipStream_t next = reinterpret_cast<hipStream_t>(hip_stream);
+  if (next == ctx->stream) return VPS_OK;
+  // Earlier calls may still be running on the old stream, and the next call reads what they leave behind: the context's own
+  // tables and partial sums, and the caller's sort workspace under VPS_FLAG_REUSE_SORT / VPS_FLAG_SHARE_ENERGY.  The new stream
+  // starts behind everything enqueued so far (a wait captures the record it follows: one event serves every switch).
+  if (!ctx->ev_switch) VPS_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_switch, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ctx->ev_switch, ctx->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(next, ctx->ev_switch, 0);
+  // switched either way: a host that destroyed the old stream first gets the error once (nothing was ordered behind that
+  // stream) and a context that works on the new one, not a dead handle that fails every later switch as well
+  ctx->stream = next;
+  if (e != hipSuccess) (void)hipGetLastError();
+  VPS_HIP_CHECK(ctx, e);
   return VPS_OK;
 }
 
@@ -202,7 +215,12 @@ int vps_memset(vps_ctx* ctx, void* dev, int value, size_t bytes) {
 int vps_memcpy_h2d(vps_ctx* ctx, void* dev, const void* host, size_t bytes) {
   VPS_ENTER(ctx);
   if ((!dev || !host) && bytes) return VPS_ERR_ARG;
-  if (bytes) VPS_HIP_CHECK(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (bytes) {
+    // in stream order, and complete on return: the host buffer is the caller's again, whatever the runtime does with a
+    // pageable source (stage it, or wait for the stream)
+    VPS_HIP_CHECK(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VPS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return VPS_OK;
 }
 

@@ -87,6 +87,9 @@ int vps_pair_k(vps_ctx* ctx, int N, const double* kx_host, const double* ky_host
   VPS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_axes, kx_host, one, hipMemcpyHostToDevice, ctx->stream));
   VPS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_axes + N, ky_host, one, hipMemcpyHostToDevice, ctx->stream));
   VPS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_axes + 2 * N, kz_host, one, hipMemcpyHostToDevice, ctx->stream));
+  // the host axes are the caller's again on return: the copies are complete, not left to how the runtime treats pageable memory
+  // (not a hot path: the un-fused binning API)
+  VPS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   const long long n3 = (long long)N * N * N;
   const long long blocks = (n3 + 255) / 256;
   if (blocks > 0x7fffffffLL) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_pair_k: N too large");

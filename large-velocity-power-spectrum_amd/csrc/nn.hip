@@ -2003,10 +2003,6 @@ static int nn_resample_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   double* dqx = ctx->d_axes;
   double* dqy = dqx + nqx;
   double* dqz = dqy + nqy;
-  // pageable-host copies: the runtime stages them before returning
-  VPS_HIP_CHECK(ctx, hipMemcpyAsync(dqx, qx_host, sizeof(double) * nqx, hipMemcpyHostToDevice, ctx->stream));
-  VPS_HIP_CHECK(ctx, hipMemcpyAsync(dqy, qy_host, sizeof(double) * nqy, hipMemcpyHostToDevice, ctx->stream));
-  VPS_HIP_CHECK(ctx, hipMemcpyAsync(dqz, qz_host, sizeof(double) * nqz, hipMemcpyHostToDevice, ctx->stream));
   char* work = reinterpret_cast<char*>(work_dev);
   double qmax = 0.0;
   for (int i = 0; i < nqx; ++i) qmax = std::fmax(qmax, std::fabs(qx_host[i]));
@@ -2025,6 +2021,12 @@ static int nn_resample_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
     for (int a = 0; a < 3; ++a)
       if (nn[a] == 1) model.h[a] = hm > 0.0 ? hm : 1.0;
   }
+  // pageable-host copies on the context's stream, AFTER every host-side check of the axes (no refusal leaves them pending):
+  // complete when this call returns, whatever the runtime does with them, because nn_run synchronises the stream for the
+  // bounding box right behind them -- the caller's axes are free on return
+  VPS_HIP_CHECK(ctx, hipMemcpyAsync(dqx, qx_host, sizeof(double) * nqx, hipMemcpyHostToDevice, ctx->stream));
+  VPS_HIP_CHECK(ctx, hipMemcpyAsync(dqy, qy_host, sizeof(double) * nqy, hipMemcpyHostToDevice, ctx->stream));
+  VPS_HIP_CHECK(ctx, hipMemcpyAsync(dqz, qz_host, sizeof(double) * nqz, hipMemcpyHostToDevice, ctx->stream));
   if (pos_is_f64)
     return nn_run<double>(ctx, reinterpret_cast<const double*>(pos_dev), payload_dev, np, C, x0, nx, nqy,
                           nqz, dqx, dqy, dqz, qmax, model, out_dev, nn_idx_dev, work, em);

@@ -25,6 +25,7 @@ struct vps_comm;   // comm.hip: RCCL communicator, communication stream, events
 struct vps_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  hipEvent_t ev_switch = nullptr;   // vps_set_stream: recorded on the stream that is left, waited for by the one that follows
   char err[512] = {0};
   int num_cu = 256;
   size_t lds_per_cu = 160 * 1024;
