@@ -104,6 +104,14 @@ enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                                               the scalar fields of a step out over several GPUs (whole grids, no exchange). */
 #define VPS_FLAG_COMPONENT(c) VPS_FLAG_COMPONENTS(1 << (c))
 #define VPS_FLAG_COMPONENT_MASK 0x70
+#define VPS_FLAG_ASSIGN(order) ((((order) - 1) & 3) << 8) /* vps_deposit_field ONLY (an addition within ABI 13): deposit [rho v, rho]
+                                              by cloud-in-cell (order 2: 0x100) or triangular-shaped cloud (order 3: 0x200) instead of
+                                              NGP, by the direct route's rule (vps_deposit_assign) with the quantity formed in the owner
+                                              brick's epilogue; see vps_deposit_field.  Order 1 is no bit at all: the NGP call.  The value
+                                              0x300, and either bit on any other entry point that takes flags (vps_deposit_fft_zy,
+                                              vps_deposit_fft_z[_slab], vps_field_algebra[_out], vps_nn_resample_quantity) or together
+                                              with VPS_FLAG_INPUT_IS_VM: VPS_ERR_ARG before anything is enqueued. */
+#define VPS_FLAG_ASSIGN_MASK 0x300
 
 /* ---- lifecycle ---------------------------------------------------------- */
 int vps_create(vps_ctx** out, int device_id);
@@ -230,7 +238,20 @@ int vps_deposit_ngp(vps_ctx* ctx, const void* pos_dev, int pos_is_f64,
  * the fly from vel_dev [np][3] and rho_dev [np], and applies the field algebra of
  * vps_field_algebra in the brick epilogue.  fields_dev: [ncomp][nx][N][N] float32,
  * ncomp = 3 (VPS_VELOCITY, VPS_MOMENTUM), 1 (VPS_ENERGY) or 4 (VPS_VM: vx,vy,vz,mass).
- * work_dev: vps_deposit_workspace_bytes(np, 4, N, nx).                              */
+ * work_dev: vps_deposit_workspace_bytes(np, 4, N, nx).
+ * With flags | VPS_FLAG_ASSIGN(order), order 2 (CIC) or 3 (TSC): the same fields of the CIC / TSC cell totals, on any x-slab.
+ * The [rho v, rho] payload is deposited by the rule of vps_deposit_assign (below: its base cell, its six weight words, its
+ * weights, the same expressions and rounding points), one sort record per particle, and the owner brick's epilogue turns the
+ * four cell totals into the quantity (every quantity code; VPS_FLAG_REFERENCE_MOMENTUM_BUG as without the bits).  Only the
+ * rows [x0, x0 + nx) are written, every cell exactly once by plain stores: no memset, no global float atomic.  Particles are
+ * replicated -- every rank passes all np -- and no halo is exchanged: the sort is keyed by the brick geometry of the WHOLE
+ * grid (that of vps_deposit_assign with C = 4), a particle none of whose `order` target rows lies in the slab is dropped by
+ * its key, and the slab's bricks gather from their lower neighbours' buckets wherever those lie.
+ * work_dev is then vps_deposit_assign_workspace_bytes(np, 4, N, order): the record arrays are sized for all np particles
+ * although a rank of G keeps about np / G of them (a slab-sized workspace would need the particles compacted first).
+ * Positions that are NaN, infinite or beyond 2^53 cells are skipped and any finite position wraps periodically, as in
+ * vps_deposit_assign; np = 0 writes the quantity of an empty grid (zeros).  Timers: the sort under VPS_K_DEPOSIT, the
+ * accumulation and epilogue under VPS_K_ALGEBRA.  The call stays a pure enqueue on the context's stream. */
 int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* vel_dev,
                       const float* rho_dev, int64_t np, int N, double Lbox, int x0, int nx,
                       int quantity, int flags, float* fields_dev, void* work_dev);
@@ -267,8 +288,9 @@ int vps_assign_expand(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
  * payload wx wy wz in LDS for the targets (c0 + j) mod N inside its own range.  Every (particle, offset) pair is counted
  * exactly once and grid_dev [C][N][N][N] float32 is OVERWRITTEN, every cell exactly once, by plain stores: no memset, no global
  * float atomic.  Sums agree with the expansion route up to float32 summation order.
- *   - the whole grid only (x0 = 0, nx = N); slabs keep the expansion route, which needs no halo exchange with replicated
- *     particles.  C in {1, 3, 4}, order 2 (CIC) or 3 (TSC); raw channels out (vps_field_algebra makes quantities of them).
+ *   - the whole grid only (x0 = 0, nx = N), raw channels out (vps_field_algebra makes quantities of them); C in {1, 3, 4},
+ *     order 2 (CIC) or 3 (TSC).  An x-slab of the QUANTITY fields of [rho v, rho] comes from vps_deposit_field with
+ *     VPS_FLAG_ASSIGN(order); a slab of raw channels keeps the expansion route.
  *   - a position whose s is NaN or infinite, or beyond 2^53 cells, is SKIPPED (it deposits nowhere); positions any finite
  *     distance outside the box below that wrap periodically like the oracle's int64 %.
  *   - np = 0 writes zeros.  Bad np / N / Lbox / C / order and null buffers: VPS_ERR_ARG with a message.

@@ -1024,8 +1024,9 @@ int check_deposit_args(vps_ctx* ctx, const char* who, int64_t np, int N, double 
 // its range on every axis (usually the -1 neighbour: at most 8 buckets), and adds payload * wx * wy * wz into its LDS tile for
 // every (record, offset) whose target cell (c0 + j) mod N lies in its own range.  Every (particle, offset) pair has exactly one
 // owner, so it is counted exactly once; every grid cell is written exactly once, by plain streaming stores, as in the NGP route:
-// no grid memset, no global float atomic.  Whole grid only (x0 = 0, nx = N): a slab would need the particles of its lower
-// neighbour's last cells, which the expansion route gets for free from replicated particles.
+// no grid memset, no global float atomic.  vps_deposit_assign writes the whole grid (x0 = 0, nx = N) of raw channels; an x-slab
+// of quantity fields comes from the fused form further down (assign_field_kernel), which keeps this key geometry and drops the
+// particles without a target row in the slab -- with replicated particles no halo is exchanged.
 //
 // c0 is the float64 rule of assign_expand_kernel -- s = (double)pos / lcell, floor(s - 1/2) for CIC, floor(s) - 1 for TSC,
 // wrapped into [0, N) BEFORE the conversion to int (wrap_cell's expression) -- never cell_of<F>, the NGP rule in the particle's
@@ -1081,6 +1082,65 @@ struct AssignPayload {
         const double d = s - (floor(s) + 0.5);
         val[CP + 2 * a] = (float)(0.5 - d);
         val[CP + 2 * a + 1] = (float)(0.5 + d);
+      }
+    }
+  }
+};
+
+// ---- the fused form on an x-slab (vps_deposit_field with VPS_FLAG_ASSIGN) --------------------------------------------------
+// The key of AssignKeyOf -- the bricks of the WHOLE grid -- with one more way of being invalid: a particle none of whose ORDER
+// target rows (c0x + j) mod N lies in [x0, x0 + nx).  Those rows are in the slab exactly when c0x lies in the window
+// [x0 - (ORDER - 1), x0 + nx - 1] mod N, i.e. (c0x - xlo) mod N < span with xlo = x0 - (ORDER - 1), span = nx + ORDER - 1; with
+// span >= N every particle passes.  The expressions of AssignKeyOf, restated (not shared: its kernels stay what they are).
+template <typename F, typename K, int ORDER>
+struct AssignSlabKeyOf {
+  const F* __restrict__ pos;
+  double lcell, n;
+  Bricks b;       // make_bricks(N, 0, N, 4): the whole grid's
+  int xlo, span;
+  __device__ __forceinline__ K operator()(long long i) const {
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double f0 = assign_base_cell<ORDER>((double)pos[i * 3 + a] / lcell);
+      const double r = f0 - floor(f0 / n) * n;          // wrap_cell, before its conversion
+      if (!(r >= 0.0 && r < n)) return sort_invalid<K>();   // NaN, inf, beyond 2^53
+      c[a] = (int)r;
+      if (a == 0) {
+        int d = c[0] - xlo;                              // in (-N, N + ORDER - 1)
+        if (d < 0) d += b.N;
+        if (d >= b.N) d -= b.N;
+        if (d >= span) return sort_invalid<K>();         // no target row in the slab
+      }
+    }
+    const int ix = c[0] / b.bx, iy = c[1] / b.by, iz = c[2] / b.bz;
+    const unsigned brick = (unsigned)((ix * b.nby + iy) * b.nbz + iz);
+    const unsigned loc = (unsigned)(((c[0] - ix * b.bx) * b.by + (c[1] - iy * b.by)) * b.bz + (c[2] - iz * b.bz));
+    return (K)brick * (unsigned)b.cells + loc;
+  }
+};
+
+// AssignPayload with the [rho v, rho] payload built on the fly (the RHOV form of load_payload), the six weight words as there
+template <typename F, int ORDER>
+struct AssignRhovPayload {
+  static constexpr int C = 4 + 6;
+  const F* __restrict__ pos;
+  const float* __restrict__ vel;
+  const float* __restrict__ rho;
+  double lcell;
+  __device__ __forceinline__ void load(long long i, float val[4 + 6]) const {
+    load_payload<4, true>(vel, rho, i, val);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double s = (double)pos[i * 3 + a] / lcell;
+      if constexpr (ORDER == 2) {
+        const double f = s - 0.5 - floor(s - 0.5);
+        val[4 + 2 * a] = (float)(1.0 - f);
+        val[4 + 2 * a + 1] = (float)f;
+      } else {
+        const double d = s - (floor(s) + 0.5);
+        val[4 + 2 * a] = (float)(0.5 - d);
+        val[4 + 2 * a + 1] = (float)(0.5 + d);
       }
     }
   }
@@ -1276,6 +1336,159 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// The fused form of the direct route on an x-slab: records {cell-in-brick of c0, [rho v, rho], 6 weight words} grouped by the
+// brick of c0 in the WHOLE grid's geometry `b` (x0 = 0, nx = N) -> the fields of QUANT on the rows [x0, x0 + nx), out
+// [NOUT][nx][N][N], every cell written exactly once.  The gather loop and its LDS float adds are assign_accumulate_kernel's with
+// C = 4, the epilogue is brick_accumulate_kernel<4, EPI_ALGEBRA, QUANT>'s (`par`: brick_par).  Three things differ from the whole
+// grid: only the bricks [first, first + nbricks) whose x range meets the slab are walked; a brick owns its cells on the rows
+// [cx0, cx1) = its x range clipped to the slab only (the other rows of its tile are never added to and never read); and the
+// stream-out addresses row gx - x0 with plane stride nx N N.
+template <int ORDER, int QUANT>
+__global__ void __launch_bounds__(256)
+    assign_field_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start, Bricks b, long long first,
+                        long long nbricks, int x0, int nx, int flags, float par, float* __restrict__ out) {
+  constexpr int C = 4, W = C + 7;
+  constexpr int NOUT = vps_quantity_channels(QUANT);
+  const int cflags = (vps_quantity_needs_alpha(QUANT) || vps_quantity_scalar_rho(QUANT)) ? 0 : flags;
+  const CellPar cpar{par, par};     // (one float, copied into both members: brick_accumulate_kernel)
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* tile = reinterpret_cast<float*>(smem_raw);  // [C][cells]
+  const int cells = b.cells, N = b.N;
+  const bool vec4 = ((b.bz & 3) == 0) && ((N & 3) == 0);
+  for (int i = threadIdx.x; i < C * cells; i += blockDim.x) tile[i] = 0.f;
+  const long long plane = (long long)nx * N * N;
+  const int rowcells = b.by * b.bz;       // cells of one x row of the tile
+  __syncthreads();
+  for (long long t = blockIdx.x; t < nbricks; t += gridDim.x) {
+    const long long brick = first + t;
+    const int iz = (int)(brick % b.nbz), iy = (int)((brick / b.nbz) % b.nby);
+    const int ix = (int)(brick / ((long long)b.nbz * b.nby));
+    const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
+    // the cells this brick owns: its range (the last brick of an axis may be partial), on x clipped to the slab
+    const int gy1 = min(gy0 + b.by, N), gz1 = min(gz0 + b.bz, N);
+    const int cx0 = max(gx0, x0), cx1 = min(min(gx0 + b.bx, N), x0 + nx);
+    int srcx[3], srcy[3], srcz[3];
+    const int nsx = assign_axis_sources(ix, b.bx, N, ORDER, srcx);
+    const int nsy = assign_axis_sources(iy, b.by, N, ORDER, srcy);
+    const int nsz = assign_axis_sources(iz, b.bz, N, ORDER, srcz);
+    for (int sx = 0; sx < nsx; ++sx)
+      for (int sy = 0; sy < nsy; ++sy)
+        for (int sz = 0; sz < nsz; ++sz) {
+          const long long sb = ((long long)srcx[sx] * b.nby + srcy[sy]) * b.nbz + srcz[sz];
+          const unsigned s = start[sb], e = start[sb + 1];
+          const int ox = srcx[sx] * b.bx, oy = srcy[sy] * b.by, oz = srcz[sz] * b.bz;     // first cell of the source brick
+          for (unsigned j = s + threadIdx.x; j < e; j += blockDim.x) {
+            const unsigned* rec = records + (size_t)j * W;
+            const int loc = (int)rec[0];
+            int lz, ly, lx;
+            if (b.pow2) {
+              lz = loc & (b.bz - 1);
+              ly = (loc >> b.sz) & (b.by - 1);
+              lx = loc >> (b.sz + b.sy);
+            } else {
+              lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
+            }
+            int tx[ORDER], ty[ORDER], tz[ORDER];
+            bool anyx = false, anyy = false, anyz = false;
+#pragma unroll
+            for (int k = 0; k < ORDER; ++k) {
+              int q = ox + lx + k;
+              if (q >= N) q %= N;
+              tx[k] = (q >= cx0 && q < cx1) ? q - gx0 : -1;
+              anyx = anyx || tx[k] >= 0;
+              q = oy + ly + k;
+              if (q >= N) q %= N;
+              ty[k] = (q >= gy0 && q < gy1) ? q - gy0 : -1;
+              anyy = anyy || ty[k] >= 0;
+              q = oz + lz + k;
+              if (q >= N) q %= N;
+              tz[k] = (q >= gz0 && q < gz1) ? q - gz0 : -1;
+              anyz = anyz || tz[k] >= 0;
+            }
+            if (!(anyx && anyy && anyz)) continue;
+            float pay[C], wx[ORDER], wy[ORDER], wz[ORDER];
+#pragma unroll
+            for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
+            assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
+            assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
+            assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
+#pragma unroll
+            for (int kx = 0; kx < ORDER; ++kx) {
+              if (tx[kx] < 0) continue;
+#pragma unroll
+              for (int ky = 0; ky < ORDER; ++ky) {
+                if (ty[ky] < 0) continue;
+#pragma unroll
+                for (int kz = 0; kz < ORDER; ++kz) {
+                  if (tz[kz] < 0) continue;
+                  const float wt = wx[kx] * wy[ky] * wz[kz];      // (the product order of assign_expand_kernel)
+                  const int at = (tx[kx] * b.by + ty[ky]) * b.bz + tz[kz];
+#pragma unroll
+                  for (int c = 0; c < C; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
+                }
+              }
+            }
+          }
+        }
+    __syncthreads();
+    // stream the owned rows out (rows of bz cells are contiguous in the slab) and zero them for the next brick
+    const int loc_lo = (cx0 - gx0) * rowcells, loc_hi = (cx1 - gx0) * rowcells;
+    if (vec4) {
+      typedef float vf4 __attribute__((ext_vector_type(4)));
+      const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int loc = loc_lo + 4 * (int)threadIdx.x; loc < loc_hi; loc += 4 * (int)blockDim.x) {
+        int lz, ly, lx;
+        if (b.pow2) {
+          lz = loc & (b.bz - 1);
+          ly = (loc >> b.sz) & (b.by - 1);
+          lx = loc >> (b.sz + b.sy);
+        } else {
+          lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
+        }
+        const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
+        const bool inside = gy < N && gz < N;      // (gx is inside by the loop's bounds; N and bz multiples of 4: whole quads)
+        const long long cell = ((long long)(gx - x0) * N + gy) * N + gz;
+        float4* t0 = reinterpret_cast<float4*>(tile + loc);
+        float4* t1 = reinterpret_cast<float4*>(tile + cells + loc);
+        float4* t2 = reinterpret_cast<float4*>(tile + 2 * cells + loc);
+        float4* t3 = reinterpret_cast<float4*>(tile + 3 * cells + loc);
+        const float4 c0 = *t0, c1 = *t1, c2 = *t2, c3 = *t3;
+        *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
+        if (inside) {
+          float rx[4], ry[4], rz[4], rw[4];
+          cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx);
+          cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry);
+          cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz);
+          cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw);
+#pragma unroll
+          for (int c = 0; c < NOUT; ++c) {
+            vf4 q; q.x = rx[c]; q.y = ry[c]; q.z = rz[c]; q.w = rw[c];
+            __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(out + c * plane + cell));
+          }
+        }
+      }
+    } else {
+      for (int loc = loc_lo + (int)threadIdx.x; loc < loc_hi; loc += (int)blockDim.x) {
+        const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
+        const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
+        float v[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          v[c] = tile[c * cells + loc];
+          tile[c * cells + loc] = 0.f;
+        }
+        if (gy >= N || gz >= N) continue;
+        const long long cell = ((long long)(gx - x0) * N + gy) * N + gz;
+        float r[4];
+        cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r);
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) __builtin_nontemporal_store(r[c], out + c * plane + cell);
+      }
+    }
+    __syncthreads();   // the owned rows are all zero again (the others were never touched)
+  }
+}
+
 // brick geometry and sort layout of the direct route: the bricks of the NGP deposit of C channels (the LDS tile holds the C
 // payload channels only), records of C + 6 channels
 struct AssignPlan {
@@ -1298,17 +1511,17 @@ int check_assign_args(vps_ctx* ctx, const char* who, int64_t np, int C, int N, i
   return VPS_OK;
 }
 
-// particles -> records grouped by the brick of c0 + start[]: sort_into_buckets with the key and payload of the direct route
-template <typename F, int C, int ORDER>
-int assign_sort(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, double lcell, const AssignPlan& p, char* work) {
-  constexpr int CR = C + 6;
-  typedef AssignPayload<F, C, ORDER> Pay;
+// particles -> records grouped by the brick of c0 + start[]: sort_into_buckets with the key and payload of the direct route.
+// pay: the payload functor (AssignPayload, AssignRhovPayload); key_of(K{}): the key functor for keys of type K (AssignKeyOf,
+// AssignSlabKeyOf).
+template <typename Pay, typename KeyMaker>
+int assign_sort(vps_ctx* ctx, const Pay& pay, KeyMaker key_of, int64_t np, const AssignPlan& p, char* work) {
+  constexpr int CR = Pay::C;
   const Bricks& b = p.b;
   const DepLayout& l = p.l;
   unsigned* count = reinterpret_cast<unsigned*>(work + l.count);
   unsigned* start = reinterpret_cast<unsigned*>(work + l.start);
   unsigned* records = reinterpret_cast<unsigned*>(work + l.records);
-  const Pay pay{pos, payload, lcell};
   vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
   if (np == 0) {
     VPS_HIP_CHECK(ctx, hipMemsetAsync(start, 0, sizeof(unsigned) * (l.nbricks + 1), ctx->stream));
@@ -1325,9 +1538,10 @@ int assign_sort(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, do
     const bool staged = sort_staged() && lds_staged <= ctx->lds_per_cu;
     auto level1 = [&](auto* keys) -> int {
       typedef typename std::remove_pointer<decltype(keys)>::type K;
-      typedef AssignKeyOf<F, K, ORDER> Key;
+      const auto key = key_of(K{});
+      typedef typename std::remove_const<decltype(key)>::type Key;
       hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, Key>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
-                         Key{pos, lcell, (double)b.N, b}, (long long)np, g, keys, table);
+                         key, (long long)np, g, keys, table);
       launch_exclusive_scan(ctx->stream, table, (long long)g.ngroups * g.nchunks, table_tiles, table_start);
       if (staged) {
         auto kern = sort_scatter_staged_kernel<SORT_ITEMS, K, Pay>;
@@ -1348,14 +1562,15 @@ int assign_sort(vps_ctx* ctx, const F* pos, const float* payload, int64_t np, do
     hipLaunchKernelGGL((sort_fine_kernel<CR, true>), dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1, g,
                        table_start, start, records);
   } else {
-    typedef AssignKeyOf<F, unsigned long long, ORDER> Key;
+    const auto key = key_of((unsigned long long)0);
+    typedef typename std::remove_const<decltype(key)>::type Key;
     unsigned* tiles = reinterpret_cast<unsigned*>(work + l.tiles);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(work + l.keys);
     unsigned* ranks = reinterpret_cast<unsigned*>(work + l.ranks);
     VPS_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(unsigned) * l.nbricks, ctx->stream));
     const unsigned pblocks = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(assign_rank_kernel<Key>, dim3(pblocks), dim3(256), 0, ctx->stream, Key{pos, lcell, (double)b.N, b},
-                       (long long)np, (unsigned)b.cells, count, keys, ranks);
+    hipLaunchKernelGGL(assign_rank_kernel<Key>, dim3(pblocks), dim3(256), 0, ctx->stream, key, (long long)np, (unsigned)b.cells,
+                       count, keys, ranks);
     launch_exclusive_scan(ctx->stream, count, l.nbricks, tiles, start);
     hipLaunchKernelGGL(assign_scatter_kernel<Pay>, dim3(pblocks), dim3(256), 0, ctx->stream, keys, ranks, pay, (long long)np,
                        (unsigned)b.cells, start, records);
@@ -1370,7 +1585,9 @@ int deposit_assign_run(vps_ctx* ctx, const void* pos_v, const float* payload, in
   const AssignPlan p = assign_plan(np, C, N);
   char* work = reinterpret_cast<char*>(work_v);
   const double lcell = Lbox / (double)N;      // float64 whatever the dtype of pos (assign_expand_kernel's)
-  const int rc = assign_sort<F, C, ORDER>(ctx, reinterpret_cast<const F*>(pos_v), payload, np, lcell, p, work);
+  const F* pos = reinterpret_cast<const F*>(pos_v);
+  const int rc = assign_sort(ctx, AssignPayload<F, C, ORDER>{pos, payload, lcell},
+                             [&](auto k) { return AssignKeyOf<F, decltype(k), ORDER>{pos, lcell, (double)N, p.b}; }, np, p, work);
   if (rc) return rc;
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
@@ -1393,6 +1610,53 @@ int deposit_assign_order(vps_ctx* ctx, const void* pos, const float* payload, in
                          float* grid, void* work) {
   return order == 2 ? deposit_assign_run<F, C, 2>(ctx, pos, payload, np, N, Lbox, grid, work)
                     : deposit_assign_run<F, C, 3>(ctx, pos, payload, np, N, Lbox, grid, work);
+}
+
+// vps_deposit_field with VPS_FLAG_ASSIGN(ORDER): the direct route's sort keyed by the whole grid's bricks with the slab's
+// window in the key, then assign_field_kernel over the bricks whose x range meets [x0, x0 + nx)
+template <typename F, int ORDER>
+int deposit_assign_field_run(vps_ctx* ctx, const void* pos_v, const float* vel, const float* rho, int64_t np, int N, double Lbox,
+                             int x0, int nx, int quantity, int flags, float* fields, void* work_v) {
+  const AssignPlan p = assign_plan(np, 4, N);
+  const Bricks& b = p.b;
+  char* work = reinterpret_cast<char*>(work_v);
+  const double lcell = Lbox / (double)N;      // float64 whatever the dtype of pos, as in the direct route
+  const F* pos = reinterpret_cast<const F*>(pos_v);
+  const int xlo = x0 - (ORDER - 1);
+  const int span = nx + ORDER - 1 >= N ? 0x7fffffff : nx + ORDER - 1;     // (the whole ring: every particle passes)
+  const int rc = assign_sort(ctx, AssignRhovPayload<F, ORDER>{pos, vel, rho, lcell},
+                             [&](auto k) { return AssignSlabKeyOf<F, decltype(k), ORDER>{pos, lcell, (double)N, b, xlo, span}; },
+                             np, p, work);
+  if (rc) return rc;
+  const float vol = (float)(lcell * lcell * lcell);
+  {
+    vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
+    const int ix_lo = x0 / b.bx, ix_hi = (x0 + nx - 1) / b.bx;
+    const long long per_x = (long long)b.nby * b.nbz;
+    const long long first = ix_lo * per_x, nbricks = (ix_hi - ix_lo + 1) * per_x;
+    const size_t lds = (size_t)4 * b.cells * sizeof(float);
+    long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    long long grid_wg = (long long)ctx->num_cu * per_cu;
+    if (grid_wg > nbricks) grid_wg = nbricks;
+    const int rcq = dispatch_quantity(quantity, [&](auto q) {
+      hipLaunchKernelGGL((assign_field_kernel<ORDER, decltype(q)::value>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+                         reinterpret_cast<const unsigned*>(work + p.l.records), reinterpret_cast<const unsigned*>(work + p.l.start),
+                         b, first, nbricks, x0, nx, flags, brick_par(ctx, decltype(q)::value, vol), fields);
+      return VPS_OK;
+    });
+    if (rcq) return vps_fail(ctx, rcq, "vps_deposit_field: quantity %d", quantity);
+  }
+  VPS_HIP_CHECK(ctx, hipGetLastError());
+  return VPS_OK;
+}
+
+// no entry point but vps_deposit_field takes the assignment bits: they would be silently ignored and the caller get NGP
+int refuse_assign_flags(vps_ctx* ctx, const char* who, int flags) {
+  if (flags & VPS_FLAG_ASSIGN_MASK)
+    return vps_fail(ctx, VPS_ERR_ARG, "%s: VPS_FLAG_ASSIGN is taken by vps_deposit_field only (flags 0x%x)", who, flags);
+  return VPS_OK;
 }
 
 }  // namespace
@@ -1460,6 +1724,16 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   if (flags & VPS_FLAG_INPUT_IS_VM) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_INPUT_IS_VM is meaningless here");
   if (!fields_dev || !work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: null buffer");
+  if (flags & VPS_FLAG_ASSIGN_MASK) {
+    const int order = ((flags & VPS_FLAG_ASSIGN_MASK) >> 8) + 1;
+    if (order != 2 && order != 3)
+      return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_ASSIGN(order): order must be 2 (CIC) or 3 (TSC), flags 0x%x", flags);
+    const int eflags = flags & ~VPS_FLAG_ASSIGN_MASK;
+#define VPS_DAF(FF, OO) deposit_assign_field_run<FF, OO>(ctx, pos_dev, vel_dev, rho_dev, np, N, Lbox, x0, nx, quantity, eflags, fields_dev, work_dev)
+    if (pos_is_f64) return order == 2 ? VPS_DAF(double, 2) : VPS_DAF(double, 3);
+    return order == 2 ? VPS_DAF(float, 2) : VPS_DAF(float, 3);
+#undef VPS_DAF
+  }
   return pos_is_f64 ? deposit_run<double, 4, true, EPI_ALGEBRA>(ctx, pos_dev, vel_dev, rho_dev, np, N, Lbox, x0,
                                                                nx, quantity, flags, fields_dev, work_dev)
                     : deposit_run<float, 4, true, EPI_ALGEBRA>(ctx, pos_dev, vel_dev, rho_dev, np, N, Lbox, x0,
@@ -1627,6 +1901,7 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
                             int flags, void* spec_dev, void* nyq_dev, void* zimg_dev, void* work_dev, int64_t np_cap) {
   int rc = check_deposit_args(ctx, "vps_deposit_fft_zy", np, N, Lbox, x0, nx);
   if (rc) return rc;
+  if ((rc = refuse_assign_flags(ctx, "vps_deposit_fft_zy", flags))) return rc;
   if (!vps_deposit_fft_zy_supported(ctx, N, quantity))
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_fft_zy: N=%d quantity=%d not supported by the fused path", N, quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_fft_zy", quantity, flags))) return rc;
@@ -1758,6 +2033,7 @@ int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, c
   VPS_ENTER(ctx);
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
   if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;
+  if (int rc = refuse_assign_flags(ctx, "vps_field_algebra", flags)) return rc;
   if (ncell < 0 || (ncell & 3)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: ncell must be a multiple of 4");
   if (ncell == 0) return VPS_OK;
   if (!chans_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: null buffer");

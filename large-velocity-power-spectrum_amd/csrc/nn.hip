@@ -1965,6 +1965,8 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
   VPS_ENTER(ctx);
   if (!(Lcell > 0) || !out_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: bad Lcell / null output");
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: quantity %d", quantity);
+  if (flags & VPS_FLAG_ASSIGN_MASK)   // (vps_deposit_field's: silently ignored here, the caller would get the NN field)
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: VPS_FLAG_ASSIGN is taken by vps_deposit_field only (flags 0x%x)", flags);
   if (int rc = vps_check_weighted(ctx, "vps_nn_resample_quantity", quantity, flags)) return rc;
   return nn_resample_impl(ctx, pos_dev, pos_is_f64, rhov_dev, np, 4, qx_host, nqx, qy_host, nqy, qz_host, nqz, x0, nx,
                           out_dev, nn_idx_dev, work_dev, nn_emit_of(ctx, quantity, flags, Lcell));

@@ -30,6 +30,7 @@ NTOT = 1000
 MAXNBOX = 500
 LTOT = 1
 remove_bulk_velocity = True
+GRIDDINGS = ("nn", "ngp", "cic", "tsc")
 
 
 def build_parser():
@@ -51,7 +52,20 @@ def build_parser():
                         "(vpower.device.resolve_quantity).  Every quantity but velocity needs PartType0/Density in the snapshot.")
     p.add_argument("--density-weight", type=float, default=None, metavar="ALPHA",
                    help="Exponent alpha of --quantity weighted_velocity (rho^alpha v) or density (rho^alpha; default 1).")
+    p.add_argument("--gridding", type=str, default="nn", choices=GRIDDINGS,
+                   help="How the particles reach the grid: nn (default: the reference's nearest-neighbour resampling, Pk.txt "
+                        "unchanged), or a mass-assignment deposit of [rho v, rho] -- ngp, cic, tsc -- with the quantity formed per "
+                        "cell (velocity = sum rho v / sum rho).  Every deposit needs PartType0/Density, --quantity velocity included.")
+    p.add_argument("--deconvolve", action="store_true",
+                   help="Divide |F(k)|^2 by the window of the --gridding assignment (ngp, cic, tsc; refused with nn).")
     return p
+
+
+def check_gridding(parser, args):
+    """--deconvolve needs a mass-assignment window: refused (parser.error) with the nearest-neighbour gridding."""
+    if args.deconvolve and args.gridding == "nn":
+        parser.error("--deconvolve divides by the window of a mass assignment: pass --gridding ngp, cic or tsc")
+    return args
 
 
 def resolve_cli_quantity(args):
@@ -139,17 +153,27 @@ def _script_table(tab):
     return tab
 
 
-def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=None, helmholtz=False, quantity=None, density=None):
+def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=None, helmholtz=False, quantity=None, density=None,
+                      gridding="nn", deconvolve=False):
     """The body of main() after loading: preprocessing, exact NN at x=i*LCELL (float32
     lattice, :343-346), raw velocity gather (:351), P(k) (:409-463).  Returns the float32
     (nbins,4) table that rank 0 saves; helmholtz=True: the tuple (total, compressive, solenoidal) of such tables
     (vpower.device.PowerPipeline.accumulate_helmholtz; total is the table of helmholtz=False).
     quantity: a code of vpower.device.resolve_quantity other than plain velocity, with `density` per particle: the fields of
-    that quantity from the nearest particle's [rho v, rho] (vps_nn_resample_quantity) instead of the raw velocity."""
+    that quantity from the nearest particle's [rho v, rho] (vps_nn_resample_quantity) instead of the raw velocity.
+    gridding "ngp" / "cic" / "tsc" instead of the default "nn": every rank deposits [rho v, rho] of the replicated particles on
+    its x-slab by that mass assignment, the quantity (the velocity included: sum rho v / sum rho) formed per cell, so `density`
+    is needed whatever the quantity; deconvolve=True then divides |F(k)|^2 by the assignment's window."""
     import torch
     from vpower import device
+    if gridding not in GRIDDINGS:
+        raise ValueError("gridding must be one of %s, not %r" % (", ".join(GRIDDINGS), gridding))
+    if deconvolve and gridding == "nn":
+        raise ValueError("deconvolve needs a mass-assignment gridding (ngp, cic, tsc), not the nearest-neighbour resampling")
+    if gridding != "nn" and density is None:
+        raise Exception("every deposit gridding needs the particle densities (the velocity is sum rho v / sum rho)")
     k = kernels if kernels is not None else device.default_kernels()
-    pipe = device.PowerPipeline(ntot, ltot, kernels=k, comm=comm, flavour="script")
+    pipe = device.PowerPipeline(ntot, ltot, kernels=k, comm=comm, flavour="script", deconvolve=gridding if deconvolve else None)
     lcell = ltot / ntot
     ax = np.array([i * lcell for i in range(ntot)], dtype=np.float32).astype(np.float64)
     # preprocessing of :280-291 on the device, in the snapshot's coordinate dtype
@@ -159,7 +183,10 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
     k.preprocess(pos, vel, k.to_device(np.asarray(mass), torch.float32), True, remove_bulk_velocity)
     # Annoy holds float32 coordinates (add_item, :308): search them as float32
     pos = pos.to(torch.float32)
-    if quantity is not None and int(quantity) != device.VELOCITY:
+    if gridding != "nn":
+        grid = k.deposit_field(pos, vel, k.to_device(np.asarray(density), torch.float32), ntot, ltot, pipe.x0, pipe.nx,
+                               quantity if quantity is not None else device.VELOCITY, assignment=gridding)
+    elif quantity is not None and int(quantity) != device.VELOCITY:
         if density is None:
             raise Exception("every quantity but the velocity needs the particle densities")
         rhov = k.density_velocity_vector(vel, k.to_device(np.asarray(density), torch.float32))
@@ -174,7 +201,8 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = check_gridding(parser, parser.parse_args(argv))
     qname, qcode = resolve_cli_quantity(args)
     import torch
     import torch.distributed as dist
@@ -210,13 +238,13 @@ def main(argv=None):
     if not ok:
         return 0
     print(f"[{datetime.datetime.now()}] Load snapshot: {args.input}", flush=True) if rank == 0 else None
-    if qname == "velocity":
+    if qname == "velocity" and args.gridding == "nn":
         coords, mass, velocity = load_particles(args.input)
         tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot, helmholtz=args.helmholtz)
     else:
         coords, mass, velocity, density = load_particles(args.input, with_density=True)
         tab = velocity_spectrum(coords, mass, velocity, args.ntot, args.ltot, helmholtz=args.helmholtz, quantity=qcode,
-                                density=density)
+                                density=density, gridding=args.gridding, deconvolve=args.deconvolve)
     if rank == 0:
         if args.helmholtz:
             tab, comp, sol = tab

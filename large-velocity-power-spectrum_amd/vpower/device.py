@@ -157,6 +157,16 @@ def bin_edges(kmin, kmax, spacing, flavour="library"):
 
 
 ASSIGNMENT_ORDER = {"ngp": 1, "cic": 2, "tsc": 3}
+FLAG_ASSIGN_MASK = 0x300      # include/vps_hip.h: VPS_FLAG_ASSIGN_MASK
+
+
+def FLAG_ASSIGN(assignment):
+    """VPS_FLAG_ASSIGN(order) of a mass assignment, the bits vps_deposit_field takes: 0 for "ngp", 0x100 for "cic", 0x200 for
+    "tsc"; any other name is a ValueError.  For callers of the C entry point, who size the workspace themselves;
+    `HipKernels.deposit_field` takes assignment= (it sizes the workspace from it) and refuses these bits in its flags=."""
+    if not isinstance(assignment, str) or assignment not in ASSIGNMENT_ORDER:
+        raise ValueError("assignment must be 'ngp', 'cic' or 'tsc', not %r" % (assignment,))
+    return ((ASSIGNMENT_ORDER[assignment] - 1) & 3) << 8
 
 
 def window_inv2_axis(Nsize, assignment):
@@ -398,14 +408,26 @@ class HipKernels:
             self._chk(self.lib.vps_set_density_weight(self.ctx, float(alpha)))
         return int(quantity)
 
-    def deposit_field(self, pos, vel, rho, N, Lbox, x0, nx, quantity, flags=0, out=None):
-        """Fused deposit of [rho v, rho] + field algebra -> [ncomp, nx, N, N] float32."""
+    def deposit_field(self, pos, vel, rho, N, Lbox, x0, nx, quantity, flags=0, out=None, assignment="ngp"):
+        """Fused deposit of [rho v, rho] + field algebra -> [ncomp, nx, N, N] float32.  assignment = "cic" / "tsc": the same
+        fields of the CIC / TSC cell totals on the slab (VPS_FLAG_ASSIGN: one sort record per particle, the quantity formed in
+        the owner brick's epilogue), from a workspace of its own sized by vps_deposit_assign_workspace_bytes."""
+        assign = FLAG_ASSIGN(assignment)
+        if int(flags) & FLAG_ASSIGN_MASK:
+            # (the workspace below is sized from `assignment`: bits arriving in `flags` would run CIC / TSC in the NGP workspace)
+            raise ValueError("deposit_field: pass the mass assignment as assignment='cic' | 'tsc', not as FLAG_ASSIGN bits in flags "
+                             "(flags 0x%x)" % int(flags))
         self._stream()
         quantity = self._set_weight(quantity)
         ncomp = NCOMP[quantity]
         if out is None:
             out = self.empty((ncomp, nx, N, N), torch.float32)
-        work = self.workspace("deposit", self.lib.vps_deposit_workspace_bytes(pos.shape[0], 4, N, nx))
+        if assign:
+            flags = int(flags) | assign
+            work = self.workspace("deposit_field_assign", self.lib.vps_deposit_assign_workspace_bytes(
+                pos.shape[0], 4, int(N), ASSIGNMENT_ORDER[assignment]))
+        else:
+            work = self.workspace("deposit", self.lib.vps_deposit_workspace_bytes(pos.shape[0], 4, N, nx))
         self._chk(self.lib.vps_deposit_field(self.ctx, self._ptr(pos), self._pos_kind(pos),
                                              self._ptr(vel, torch.float32), self._ptr(rho, torch.float32),
                                              pos.shape[0], N, float(Lbox), x0, nx, quantity, flags,

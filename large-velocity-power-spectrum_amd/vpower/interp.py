@@ -229,13 +229,19 @@ class GasParticles:
         spectrum by the assignment window.  `method` says how: "expand" writes every particle out as 8 / 27
         weighted sub-particles for the NGP deposit, "direct" sorts one record per particle and lets every
         brick gather from its neighbours (the same grid up to float32 summation order, an order^3-th of the
-        sort and the workspace); with "ngp" both are the NGP route."""
+        sort and the workspace); "fused" does what "direct" does but returns a LAZY field, like the NGP one: its `spctrm` /
+        `helmholtz_spctrm` deposit straight into the fields of the quantity (the per-cell algebra runs in the brick's epilogue:
+        no raw channels in HBM, no algebra pass) and its grids are built on first use.  With "ngp" all three are the NGP route."""
         _check_method(method)
         k = _kernels()
         vel, rho = self._device_vel(k), self._device_rho(k)
         if assignment != "ngp":
             if assignment not in _dev.ASSIGNMENT_ORDER:
                 raise Exception("assignment must be 'ngp', 'cic' or 'tsc'")
+            if method == "fused":
+                box = BoxField._from_particles((self._device_pos(k), vel, rho), Nsize, self.Lbox)
+                box.assignment = assignment
+                return box
             if method == "direct":
                 grid = k.deposit_assign(self._device_pos(k), self._device_payload(k), Nsize, self.Lbox, assignment)
             else:
@@ -321,7 +327,8 @@ class BoxField:
         self._nn_src = None
         src = getattr(self, "_src", None)
         if src is not None and self._chans is None and not self._host:
-            self._chans = _kernels().deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, _dev.VM)
+            self._chans = _kernels().deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, _dev.VM,
+                                                   assignment=getattr(self, "assignment", "ngp"))
         self._src = None
 
     def _get(self, name, ch):
@@ -388,6 +395,12 @@ class BoxField:
         Supported: 'velocity', 'momentum', 'energy', 'weighted_velocity' (with density_weight=alpha), 'rho13_velocity',
         'rho12_velocity', 'density' (density_weight=alpha optional), 'log_density'.""")
 
+    def _assigned_fields(self, k, src, quantity, qcode):
+        """The fields of a quantity of a lazy CIC / TSC field: one fused deposit of the particles src = (pos, vel, rho)."""
+        flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
+        f = k.deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, qcode, flags, assignment=self.assignment)
+        return [f[i] for i in range(f.shape[0])]
+
     def _power(self, quantity):
         k = _kernels()
         return _expand_half_power(k.power_grid(self._fields(k, quantity), self.Nsize), self.Lbox, self.Nsize)
@@ -443,6 +456,9 @@ class BoxField:
                                   flavour="library", kmin=kmin, kmax=kmax, kres=kres,
                                   deconvolve=(getattr(self, "assignment", "ngp") if deconvolve else None))
         src = getattr(self, "_src", None)
+        if src is not None and getattr(self, "assignment", "ngp") != "ngp":
+            # particle-backed CIC / TSC field (deposit_to_field(..., method="fused")): particles -> the fields of this quantity
+            return PowerSpectrum(pipe.spectrum(self._assigned_fields(k, src, quantity, qcode)))
         if src is not None and k.fused_supported(self.Nsize, qcode):
             # particle-backed field: particles -> z/y-transformed spectra in one go (no grid in HBM)
             flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
@@ -495,7 +511,9 @@ class BoxField:
         flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
         src = getattr(self, "_src", None)
         nn = getattr(self, "_nn_src", None)
-        if src is not None and k.fused_supported(self.Nsize, qcode):
+        if src is not None and getattr(self, "assignment", "ngp") != "ngp":
+            tabs = pipe.spectrum_helmholtz(self._assigned_fields(k, src, quantity, qcode))
+        elif src is not None and k.fused_supported(self.Nsize, qcode):
             pipe.prepare()
             with k.binning_only():      # the spectra go straight into the binning pass
                 spec, nyq = k.deposit_fft_zy(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize,
@@ -560,13 +578,14 @@ def check_conservation(gasParticles, boxField) -> tuple:
 # --------------------------------------------------------------------------- #
 # free functions
 # --------------------------------------------------------------------------- #
-METHODS = ("expand", "direct")
+METHODS = ("expand", "direct")      # how the raw channels of a CIC / TSC grid are made
+FUSED = "fused"                     # GasParticles.deposit_to_field only: quantity fields straight from the particles
 
 
 def _check_method(method):
     """The `method=` of the higher-order assignments; checked before anything touches the device."""
-    if method not in METHODS:
-        raise ValueError("method must be 'expand' or 'direct', not %r" % (method,))
+    if method not in METHODS and method != FUSED:
+        raise ValueError("method must be 'expand', 'direct' or 'fused', not %r" % (method,))
 
 
 def deposit_to_grid(f, pos, Nsize, Lbox, assignment="ngp", method="expand"):
@@ -575,6 +594,9 @@ def deposit_to_grid(f, pos, Nsize, Lbox, assignment="ngp", method="expand"):
     (extension) spreads every particle over 8 / 27 cells: `method` = "expand" as weighted sub-particles through
     the NGP deposit, "direct" with one sort record per particle (GasParticles.deposit_to_field)."""
     _check_method(method)
+    if method == "fused":
+        raise ValueError("method 'fused' forms quantity fields of [rho v, rho] (GasParticles.deposit_to_field); the raw channels "
+                         "of deposit_to_grid take 'expand' or 'direct'")
     k = _kernels()
     f = np.asarray(f)
     f2 = f[:, None] if f.ndim == 1 else f

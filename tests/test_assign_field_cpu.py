@@ -1,0 +1,141 @@
+"""Host-side pins of the fused CIC / TSC deposit on x-slabs (vps_deposit_field with VPS_FLAG_ASSIGN): the flag values, the
+unchanged ABI and symbol set, the Python flag helper, the `method=` keyword, the driver's command line and the slab window of
+the sort key restated in numpy.  No GPU needed."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+import small_ref as sr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "vps_hip.h")
+SCRIPTS = os.path.join(ROOT, "large-velocity-power-spectrum_amd", "scripts")
+
+
+def _header():
+    with open(HEADER) as f:
+        return f.read()
+
+
+def test_header_defines_the_assign_flags_disjoint_from_the_others():
+    text = _header()
+    m = re.search(r"#define VPS_FLAG_ASSIGN\(order\) \(\(\(\(order\) - 1\) & 3\) << 8\)", text)
+    assert m, "VPS_FLAG_ASSIGN(order) = (((order) - 1) & 3) << 8"
+    mask = re.search(r"#define VPS_FLAG_ASSIGN_MASK (0x[0-9a-fA-F]+)", text)
+    assert mask and int(mask.group(1), 16) == 0x300
+    assign = lambda order: ((order - 1) & 3) << 8      # noqa: E731
+    assert (assign(1), assign(2), assign(3)) == (0, 0x100, 0x200)
+    others = {name: int(val, 0) for name, val in re.findall(r"#define (VPS_FLAG_[A-Z_]+) (0x[0-9a-fA-F]+|\d+)\b", text)
+              if name != "VPS_FLAG_ASSIGN_MASK"}
+    assert {"VPS_FLAG_REFERENCE_MOMENTUM_BUG", "VPS_FLAG_INPUT_IS_VM", "VPS_FLAG_REUSE_SORT", "VPS_FLAG_SHARE_ENERGY",
+            "VPS_FLAG_COMPONENT_MASK"} <= set(others), others
+    for name, val in others.items():
+        assert val & 0x300 == 0, (name, hex(val))
+
+
+def test_abi_and_symbol_set_are_unchanged():
+    from vpower import _ffi
+    text = _header()
+    assert re.search(r"#define VPS_ABI_VERSION 13\b", text) and _ffi.ABI_VERSION == 13
+    body = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    declared = set(re.findall(r"\b(vps_[a-z0-9_]+)\s*\(", body))
+    assert declared == {name for name, _, _ in _ffi.SYMBOLS}
+    assert len(declared) == 81, len(declared)      # the parent's count: the feature enters through vps_deposit_field's flags
+
+
+def test_device_flag_helper():
+    from vpower import device
+    # deposit_field sizes the workspace from assignment=: the bits in flags= are refused before the object is even touched
+    for bits in (0x100, 0x200, 0x300, 0x101):
+        for a in ("ngp", "cic", "tsc"):
+            with pytest.raises(ValueError, match="assignment="):
+                device.HipKernels.deposit_field(object(), None, None, None, 16, 1.0, 0, 16, device.VELOCITY, flags=bits, assignment=a)
+    assert device.FLAG_ASSIGN("ngp") == 0 and device.FLAG_ASSIGN("cic") == 0x100 and device.FLAG_ASSIGN("tsc") == 0x200
+    assert device.FLAG_ASSIGN_MASK == 0x300
+    for bad in ("pcs", "CIC", None, 2, ""):
+        with pytest.raises(ValueError, match="assignment"):
+            device.FLAG_ASSIGN(bad)
+    taken = (device.FLAG_REFERENCE_MOMENTUM_BUG | device.FLAG_INPUT_IS_VM | device.FLAG_REUSE_SORT | device.FLAG_SHARE_ENERGY | 0x70)
+    assert taken & device.FLAG_ASSIGN_MASK == 0
+
+
+def test_method_keyword_takes_fused():
+    from vpower import interp
+    for ok in ("expand", "direct", "fused"):
+        interp._check_method(ok)
+    for bad in ("scatter", None, "Direct", "Fused"):
+        with pytest.raises(ValueError, match="method"):
+            interp._check_method(bad)
+    pos, f = np.zeros((4, 3)), np.ones(4)
+    with pytest.raises(ValueError, match="fused"):          # raw channels have no fused form; refused before the device
+        interp.deposit_to_grid(f, pos, 16, 1.0, assignment="cic", method="fused")
+
+
+@pytest.fixture()
+def po():
+    sys.path.insert(0, SCRIPTS)
+    try:
+        import parallel_optimized
+        yield parallel_optimized
+    finally:
+        sys.path.remove(SCRIPTS)
+
+
+def test_cli_gridding_and_deconvolve(po, capsys):
+    parser = po.build_parser()
+    a = po.check_gridding(parser, parser.parse_args([]))
+    assert a.gridding == "nn" and a.deconvolve is False
+    for g in ("nn", "ngp", "cic", "tsc"):
+        assert parser.parse_args(["--gridding", g]).gridding == g
+    a = po.check_gridding(parser, parser.parse_args(["--gridding", "tsc", "--deconvolve", "--quantity", "momentum"]))
+    assert (a.gridding, a.deconvolve, a.quantity) == ("tsc", True, "momentum")
+    with pytest.raises(SystemExit):
+        parser.parse_args(["--gridding", "pcs"])
+    for argv in (["--deconvolve"], ["--deconvolve", "--gridding", "nn"]):
+        with pytest.raises(SystemExit):
+            po.check_gridding(parser, parser.parse_args(argv))
+        assert "--deconvolve" in capsys.readouterr().err
+    with pytest.raises(SystemExit):                             # main() refuses it before anything is loaded
+        po.main(["--deconvolve", "-f"])
+    import inspect
+    sig = inspect.signature(po.velocity_spectrum)
+    assert sig.parameters["gridding"].default == "nn" and sig.parameters["deconvolve"].default is False
+
+
+def _key_keeps(c0x, N, x0, nx, order):
+    """The slab window of the sort key (csrc/deposit.hip: AssignSlabKeyOf), restated: a particle with base cell c0x is kept
+    unless ((c0x - (x0 - (order - 1))) mod N) >= nx + order - 1; with nx + order - 1 >= N every particle is kept."""
+    span = nx + order - 1
+    if span >= N:
+        return np.ones(len(c0x), dtype=bool)
+    return (c0x - (x0 - (order - 1))) % N < span
+
+
+@pytest.mark.parametrize("assignment", ["cic", "tsc"])
+def test_key_window_keeps_exactly_the_particles_with_a_target_row_in_the_slab(assignment):
+    """Guards the FORMULA of the slab window, not the kernel: `_key_keeps` restates AssignSlabKeyOf's test in numpy and is held
+    against the target rows small_ref gives, so it says the rule documented in the header and DESIGN.md is the right one.  It
+    does not read the device code (it passes with or without it); that the kernel applies this rule is what the per-slab
+    lattice cases of tests/test_gpu_assign_field.py show."""
+    N, L, order = 16, 1.0, sr.ORDER[assignment]
+    rng = np.random.default_rng(order)
+    lc = L / N
+    pos = np.concatenate([rng.random((4000, 3)) * 3 * L - L,                                   # inside and a box length outside
+                          np.stack([np.arange(-N, 2 * N) * lc, np.zeros(3 * N), np.zeros(3 * N)], axis=1),          # faces
+                          np.stack([(np.arange(-N, 2 * N) + 0.5) * lc, np.zeros(3 * N), np.zeros(3 * N)], axis=1)])  # centres
+    c0, _ = sr.assign_weights(pos, N, L, assignment)
+    c0x = np.asarray(c0)[:, 0] % N
+    rows = (c0x[:, None] + np.arange(order)[None, :]) % N            # the particle's target rows
+    dropped = 0
+    for G in (2, 4, 8, 16):
+        nx = N // G
+        for x0 in (0, N - nx):                                        # the window wraps below 0; the last slab's targets wrap to row 0
+            want = ((rows - x0) % N < nx).any(axis=1)
+            got = _key_keeps(c0x, N, x0, nx, order)
+            assert np.array_equal(got, want), (G, x0, np.flatnonzero(got != want)[:5])
+            dropped += int((~want).sum())
+    assert dropped > 0
+    assert _key_keeps(c0x, N, 0, N - 1, order).all() and _key_keeps(c0x, N, 1, N - 1, order).all()
