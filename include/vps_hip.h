@@ -80,7 +80,10 @@ enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                     VPS_VM = 3 /* BoxField form: v in channels 0..2, mass in channel 3 */,
                     VPS_WEIGHTED_VELOCITY = 4 /* ABI 8: w = rho^alpha v, alpha from vps_set_density_weight (below) */,
                     VPS_DENSITY = 5 /* ABI 11: the scalar s = rho^alpha (alpha = 1: the density itself), see below */,
-                    VPS_LOG_DENSITY = 6 /* ABI 11: the scalar s = ln rho */ };
+                    VPS_LOG_DENSITY = 6 /* ABI 11: the scalar s = ln rho */,
+                    /* an addition within ABI 13, vps_deposit_field ONLY: scalars of the second moment S2 = sum w rho_p |v_p|^2 of
+                       a cell's contributions, see "Sub-grid velocity dispersion" below */
+                    VPS_TOTAL_ENERGY = 7, VPS_SUBGRID_ENERGY = 8, VPS_DISPERSION = 9 };
 /* flags for vps_field_algebra */
 #define VPS_FLAG_REFERENCE_MOMENTUM_BUG 1 /* py=pz=vx*mass as interp.py:523-525 */
 #define VPS_FLAG_INPUT_IS_VM 2             /* channels already hold vx,vy,vz,mass (a BoxField) */
@@ -172,6 +175,24 @@ int vps_set_density_weight(vps_ctx* ctx, double alpha);
  * VPS_FLAG_REFERENCE_MOMENTUM_BUG.  Outside the contract, as for the weighted velocity: densities that are float32 denormals
  * or negative, powers rho^alpha beyond the float32 range. */
 
+/* Sub-grid velocity dispersion (an addition within ABI 13: no new symbol; an extension): three SCALAR quantities, one output
+ * channel each, of what a cell's particles do around its mean velocity.  The sums run over the contributions to a cell, each
+ * with its weight w (1 for NGP, the CIC / TSC weight with VPS_FLAG_ASSIGN); vol = Lcell^3; S2 = sum w rho_p |v_p|^2, formed per
+ * contribution as (px^2 + py^2 + pz^2) / rho_p from its [rho v, rho] record (0 where rho_p = 0) and kept in a FIFTH channel of
+ * the brick's LDS tile; P = sum w rho v and R = sum w rho are the four channels every quantity is made of:
+ *   VPS_TOTAL_ENERGY    vol S2                         the kinetic energy of the cell's particles (no factor 1/2, as VPS_ENERGY)
+ *   VPS_SUBGRID_ENERGY  vol (S2 - |P|^2 / R), >= 0     the part VPS_ENERGY = vol |P|^2 / R does not resolve
+ *   VPS_DISPERSION      (S2 - |P|^2 / R) / R, >= 0     sigma^2 = <|v|^2> - |<v>|^2, density weighted
+ * all 0 in a cell without mass; the difference is clamped at 0 from below and is exactly 0 in a cell with one NGP contribution.
+ * VPS_ENERGY + VPS_SUBGRID_ENERGY = VPS_TOTAL_ENERGY cell by cell up to float32 rounding (the sub-grid energy subtracts the
+ * resolved energy exactly as VPS_ENERGY forms it: the sum is the total to the rounding of that one subtraction), and the sum of VPS_TOTAL_ENERGY over
+ * the cells is vol sum_p rho_p |v_p|^2 for NGP, CIC and TSC alike (the weights of a particle sum to 1).
+ * Taken by vps_deposit_field ALONE (NGP and VPS_FLAG_ASSIGN(2 | 3), any x-slab, the workspaces of the 4-channel call).
+ * VPS_ERR_ARG with a message naming the quantity, before anything is enqueued: vps_field_algebra[_out] (a 4-channel grid does
+ * not hold a second moment), vps_nn_resample_quantity (one nearest particle has no dispersion), vps_deposit_fft_zy /
+ * vps_deposit_fft_z[_slab] (vps_deposit_fft_zy_supported returns 0), and the codes with VPS_FLAG_REFERENCE_MOMENTUM_BUG or
+ * VPS_FLAG_INPUT_IS_VM.  VPS_ERR_UNSUPPORTED, before anything is enqueued: a device whose LDS does not hold the 5-channel tile. */
+
 /* ---- memory helpers (so the library is usable without torch) ------------ */
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);
 int vps_free(vps_ctx* ctx, void* dev);
@@ -251,7 +272,11 @@ int vps_deposit_ngp(vps_ctx* ctx, const void* pos_dev, int pos_is_f64,
  * although a rank of G keeps about np / G of them (a slab-sized workspace would need the particles compacted first).
  * Positions that are NaN, infinite or beyond 2^53 cells are skipped and any finite position wraps periodically, as in
  * vps_deposit_assign; np = 0 writes the quantity of an empty grid (zeros).  Timers: the sort under VPS_K_DEPOSIT, the
- * accumulation and epilogue under VPS_K_ALGEBRA.  The call stays a pure enqueue on the context's stream. */
+ * accumulation and epilogue under VPS_K_ALGEBRA.  The call stays a pure enqueue on the context's stream.
+ * VPS_TOTAL_ENERGY, VPS_SUBGRID_ENERGY, VPS_DISPERSION (an addition within ABI 13; "Sub-grid velocity dispersion" above):
+ * ncomp = 1, with and without VPS_FLAG_ASSIGN, the same sort records and the same workspaces; the brick's LDS tile carries a
+ * fifth channel S2 = sum w rho_p |v_p|^2 (5 cells floats: 40 KiB, 80 KiB from N = 1024 on; VPS_ERR_UNSUPPORTED before anything
+ * is enqueued where the context's LDS does not hold it), zeroed and streamed out with the other four. */
 int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* vel_dev,
                       const float* rho_dev, int64_t np, int N, double Lbox, int x0, int nx,
                       int quantity, int flags, float* fields_dev, void* work_dev);

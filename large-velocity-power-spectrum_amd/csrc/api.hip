@@ -438,3 +438,14 @@ int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags) {
     return vps_fail(ctx, VPS_ERR_ARG, "%s: %s takes neither VPS_FLAG_SHARE_ENERGY nor VPS_FLAG_REFERENCE_MOMENTUM_BUG", who, name);
   return VPS_OK;
 }
+
+const char* vps_second_moment_name(int quantity) {
+  static const char* const names[] = {"VPS_TOTAL_ENERGY", "VPS_SUBGRID_ENERGY", "VPS_DISPERSION"};
+  return vps_quantity_second_moment(quantity) ? names[quantity - VPS_TOTAL_ENERGY] : "";
+}
+
+int vps_refuse_second_moment(vps_ctx* ctx, const char* who, int quantity, const char* why) {
+  if (!vps_quantity_second_moment(quantity)) return VPS_OK;
+  return vps_fail(ctx, VPS_ERR_ARG, "%s: quantity %d (%s) is formed by vps_deposit_field only: %s", who, quantity,
+                  vps_second_moment_name(quantity), why);
+}

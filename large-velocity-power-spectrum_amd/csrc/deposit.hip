@@ -432,13 +432,43 @@ __device__ __forceinline__ void weighted_cell(float a, float b, float c, float r
 //   par.vol   the cell volume -- for the scalar density quantities its INVERSE (all they need one for: rho = mass * inv_vol of a
 //             [v, mass] field; rho is channel 3 itself otherwise)
 //   par.alpha the exponent of VPS_WEIGHTED_VELOCITY / VPS_DENSITY
+//   s2        the cell's second moment sum w rho_p |v_p|^2, for the quantities that need one (vps_quantity_second_moment: the
+//             5-channel kernels pass it, nobody else has one)
 struct CellPar {
   float vol, alpha;
 };
+// The contribution rho_p |v_p|^2 of one [rho v, rho] record to the second moment, formed in the accumulating lane: a correctly
+// rounded division (exact for integer v and a power of two rho), 0 for a record without mass.
+__device__ __forceinline__ float second_moment_term(float px, float py, float pz, float rho) {
+  return rho != 0.f ? ((px * px + py * py) + pz * pz) / rho : 0.f;
+}
 template <int QUANT>
-__device__ __forceinline__ void cell_quantity(float a, float b, float c, float rho, int flags, CellPar par, float out[4]) {
+__device__ __forceinline__ void cell_quantity(float a, float b, float c, float rho, int flags, CellPar par, float out[4],
+                                              float s2 = 0.f) {
   static_assert(vps_quantity_valid(QUANT), "a quantity code of include/vps_hip.h");
-  if constexpr (vps_quantity_scalar_rho(QUANT)) {
+  if constexpr (vps_quantity_second_moment(QUANT)) {
+    // VPS_TOTAL_ENERGY vol S2; VPS_SUBGRID_ENERGY vol (S2 - |P|^2 / R); VPS_DISPERSION (S2 - |P|^2 / R) / R.  d = S2 - |P|^2 / R
+    // with the resolved part as second_moment_term of the cell totals: in a cell with ONE NGP contribution that is the same
+    // expression of the same numbers as S2 and d is exactly 0.  Clamped at 0 (rounding can take the difference below it); a
+    // cell without mass has S2 = 0 and gives 0.
+    // The sub-grid ENERGY is the complement of VPS_ENERGY: where d > 0 it is vol S2 minus the resolved energy AS VPS_ENERGY
+    // FORMS IT (algebra_cell, bit for bit: a hardware reciprocal and nine roundings of its own), so that
+    // VPS_ENERGY + VPS_SUBGRID_ENERGY = VPS_TOTAL_ENERGY holds to the rounding of this one subtraction and not to the error of
+    // the two epilogues against each other.
+    if constexpr (QUANT == VPS_TOTAL_ENERGY) {
+      out[0] = par.vol * s2;
+    } else {
+      const float d = s2 - second_moment_term(a, b, c, rho);
+      if constexpr (QUANT == VPS_SUBGRID_ENERGY) {
+        float e[4];
+        algebra_cell(a, b, c, rho, VPS_ENERGY, 0, par.vol, e);
+        out[0] = d > 0.f ? fmaxf(par.vol * s2 - e[0], 0.f) : 0.f;
+      } else {
+        out[0] = (d > 0.f && rho != 0.f) ? d / rho : 0.f;
+      }
+    }
+    out[1] = out[2] = out[3] = 0.f;
+  } else if constexpr (vps_quantity_scalar_rho(QUANT)) {
     out[0] = vps_rho_scalar((flags & VPS_FLAG_INPUT_IS_VM) ? rho * par.vol : rho, QUANT, par.alpha);
     out[1] = out[2] = out[3] = 0.f;
   } else if constexpr (QUANT == VPS_WEIGHTED_VELOCITY) {
@@ -448,16 +478,36 @@ __device__ __forceinline__ void cell_quantity(float a, float b, float c, float r
   }
 }
 
-// run-time quantity code -> template argument: f(std::integral_constant<int, QUANT>) of the (valid) code
-template <typename Fn>
+// run-time quantity code -> template argument: f(std::integral_constant<int, QUANT>) of the (valid) code.  SECOND_MOMENT: the
+// caller's kernels carry the fifth tile channel (the two deposit kernels of vps_deposit_field); everybody else has no
+// instantiation for those codes and gets VPS_ERR_ARG.
+template <bool SECOND_MOMENT = false, typename Fn>
 int dispatch_quantity(int quantity, Fn&& f) {
   switch (quantity) {
 #define VPS_Q(Q) case Q: return f(std::integral_constant<int, Q>{})
     VPS_Q(VPS_VELOCITY); VPS_Q(VPS_MOMENTUM); VPS_Q(VPS_ENERGY); VPS_Q(VPS_VM);
     VPS_Q(VPS_WEIGHTED_VELOCITY); VPS_Q(VPS_DENSITY); VPS_Q(VPS_LOG_DENSITY);
-#undef VPS_Q
   }
+  if constexpr (SECOND_MOMENT) {
+    switch (quantity) {
+      VPS_Q(VPS_TOTAL_ENERGY); VPS_Q(VPS_SUBGRID_ENERGY); VPS_Q(VPS_DISPERSION);
+    }
+  }
+#undef VPS_Q
   return VPS_ERR_ARG;
+}
+
+// LDS tile of a deposit kernel that forms `quantity` from C record channels over `cells` cells: one more channel for the
+// second moment (80 KiB where the 4-channel tile has 64: the launch raises the kernel's limit first).
+size_t tile_bytes(int C, int cells, int quantity) {
+  return (size_t)(C + (vps_quantity_second_moment(quantity) ? 1 : 0)) * cells * sizeof(float);
+}
+// ... and a context whose LDS does not hold the 5-channel tile refuses the quantity
+int check_second_moment_tile(vps_ctx* ctx, int quantity, size_t lds) {
+  if (vps_quantity_second_moment(quantity) && lds > ctx->lds_per_cu)
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_field: quantity %d (%s) needs an LDS tile of %zu bytes, the device has %zu per CU",
+                    quantity, vps_second_moment_name(quantity), lds, ctx->lds_per_cu);
+  return VPS_OK;
 }
 
 // QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count.  `par` is the ONE float that epilogue
@@ -475,17 +525,22 @@ __global__ void __launch_bounds__(256)
   // par.vol (the volume) and never par.alpha; QUANT >= VPS_WEIGHTED_VELOCITY reads par.alpha and, with cflags = 0, never par.vol,
   // which is MEANINGLESS for them here (it holds alpha).  A two-float kernel argument would move this kernel's code.
   const CellPar cpar{par, par};
+  // The second-moment quantities (compile time: nothing of it exists in the other instantiations) keep S2 = sum rho_p |v_p|^2 in
+  // a channel of its own behind the C record channels: CT tile channels, the records stay [rho v, rho].
+  constexpr bool M2 = EPI == EPI_ALGEBRA && vps_quantity_second_moment(QUANT);
+  constexpr int CT = M2 ? C + 1 : C;
+  static_assert(!M2 || C == 4, "the second moment is formed from [rho v, rho] records");
   // Persistent workgroups walk the bricks: the streaming stores of one brick stay in flight
   // while the next bucket is being accumulated, and the tile is re-zeroed as it is read.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* tile = reinterpret_cast<float*>(smem_raw);  // [C][cells]
+  float* tile = reinterpret_cast<float*>(smem_raw);  // [CT][cells]
   const int cells = b.cells;
   const bool vec4 = ((b.bz & 3) == 0) && ((b.N & 3) == 0);
   if ((cells & 3) == 0) {
-    for (int i = threadIdx.x; i < C * cells / 4; i += blockDim.x)
+    for (int i = threadIdx.x; i < CT * cells / 4; i += blockDim.x)
       reinterpret_cast<float4*>(tile)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   } else {
-    for (int i = threadIdx.x; i < C * cells; i += blockDim.x) tile[i] = 0.f;
+    for (int i = threadIdx.x; i < CT * cells; i += blockDim.x) tile[i] = 0.f;
   }
   const long long plane = (long long)b.nx * b.N * b.N;
   long long brick = blockIdx.x;
@@ -501,6 +556,9 @@ __global__ void __launch_bounds__(256)
       const unsigned loc = rec[0];
 #pragma unroll
       for (int c = 0; c < C; ++c) atomicAdd(&tile[c * cells + loc], __uint_as_float(rec[1 + c]));   // (vps_lds_add: slower here)
+      if constexpr (M2)
+        atomicAdd(&tile[C * cells + loc], second_moment_term(__uint_as_float(rec[1]), __uint_as_float(rec[2]),
+                                                             __uint_as_float(rec[3]), __uint_as_float(rec[4])));
     }
     // bucket bounds of the next brick: in flight during the stream-out below
     const long long nb = brick + gridDim.x;
@@ -544,12 +602,18 @@ __global__ void __launch_bounds__(256)
           float4* t3 = reinterpret_cast<float4*>(tile + 3 * cells + loc);
           const float4 c0 = *t0, c1 = *t1, c2 = *t2, c3 = *t3;
           *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
+          float4 c4 = zero4;                       // the second moment (M2 only: a constant elsewhere)
+          if constexpr (M2) {
+            float4* t4 = reinterpret_cast<float4*>(tile + 4 * cells + loc);
+            c4 = *t4;
+            *t4 = zero4;
+          }
           if (inside) {
             float rx[4], ry[4], rz[4], rw[4];
-            cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx);
-            cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry);
-            cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz);
-            cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw);
+            cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
+            cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
+            cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
+            cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
 #pragma unroll
             for (int c = 0; c < NOUT; ++c)
               {   // streaming store: the grid is written once; the cache should keep the records (-33 %)
@@ -564,9 +628,9 @@ __global__ void __launch_bounds__(256)
       for (int loc = threadIdx.x; loc < cells; loc += blockDim.x) {
         const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
-        float v[C];
+        float v[CT];
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
+        for (int c = 0; c < CT; ++c) {
           v[c] = tile[c * cells + loc];
           tile[c * cells + loc] = 0.f;
         }
@@ -577,7 +641,7 @@ __global__ void __launch_bounds__(256)
           for (int c = 0; c < C; ++c) grid[c * plane + cell] = v[c];
         } else {
           float r[4];
-          cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r);
+          cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, M2 ? v[CT - 1] : 0.f);
 #pragma unroll
           for (int c = 0; c < NOUT; ++c) grid[c * plane + cell] = r[c];
         }
@@ -964,23 +1028,31 @@ int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const flo
   unsigned* start = reinterpret_cast<unsigned*>(work + l.start);
   unsigned* records = reinterpret_cast<unsigned*>(work + l.records);
   const float vol = (float)((Lbox / (double)N) * (Lbox / (double)N) * (Lbox / (double)N));
+  // (the fifth channel of the second-moment quantities: the records and the sort know nothing of it, the tile does)
+  const size_t lds = tile_bytes(C, b.cells, EPI == EPI_ALGEBRA ? quantity : VPS_VELOCITY);
+  if (int rcl = check_second_moment_tile(ctx, quantity, lds)) return rcl;      // before anything is enqueued
   const int rc = sort_into_buckets<F, C, RHOV>(ctx, pos, payload, rho, np, lcell, nsz, b, l, work);
   if (rc) return rc;
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
-    const size_t lds = (size_t)C * b.cells * sizeof(float);
     long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
     long long grid_wg = (long long)ctx->num_cu * per_cu;
     if (grid_wg > l.nbricks) grid_wg = l.nbricks;
-    auto launch = [&](auto q) {
-      hipLaunchKernelGGL((brick_accumulate_kernel<C, EPI, decltype(q)::value>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+    auto launch = [&](auto q) -> int {
+      auto kern = brick_accumulate_kernel<C, EPI, decltype(q)::value>;
+      if (lds > 64 * 1024)
+        VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
                          records, start, b, l.nbricks, flags, brick_par(ctx, decltype(q)::value, vol), grid);
       return VPS_OK;
     };
-    if constexpr (EPI == EPI_RAW) launch(std::integral_constant<int, VPS_VELOCITY>{});   // (no quantity: the one raw instantiation)
-    else if (int rcq = dispatch_quantity(quantity, launch)) return vps_fail(ctx, rcq, "deposit: quantity %d", quantity);
+    if constexpr (EPI == EPI_RAW) {
+      if (int rcl = launch(std::integral_constant<int, VPS_VELOCITY>{})) return rcl;   // (no quantity: the one raw instantiation)
+    } else if (int rcq = dispatch_quantity<true>(quantity, launch)) {
+      return rcq == VPS_ERR_HIP ? rcq : vps_fail(ctx, rcq, "deposit: quantity %d", quantity);
+    }
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;
@@ -1351,11 +1423,14 @@ __global__ void __launch_bounds__(256)
   constexpr int NOUT = vps_quantity_channels(QUANT);
   const int cflags = (vps_quantity_needs_alpha(QUANT) || vps_quantity_scalar_rho(QUANT)) ? 0 : flags;
   const CellPar cpar{par, par};     // (one float, copied into both members: brick_accumulate_kernel)
+  // (compile time, as there: the second-moment quantities keep S2 = sum w rho_p |v_p|^2 in a fifth tile channel)
+  constexpr bool M2 = vps_quantity_second_moment(QUANT);
+  constexpr int CT = M2 ? C + 1 : C;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* tile = reinterpret_cast<float*>(smem_raw);  // [C][cells]
+  float* tile = reinterpret_cast<float*>(smem_raw);  // [CT][cells]
   const int cells = b.cells, N = b.N;
   const bool vec4 = ((b.bz & 3) == 0) && ((N & 3) == 0);
-  for (int i = threadIdx.x; i < C * cells; i += blockDim.x) tile[i] = 0.f;
+  for (int i = threadIdx.x; i < CT * cells; i += blockDim.x) tile[i] = 0.f;
   const long long plane = (long long)nx * N * N;
   const int rowcells = b.by * b.bz;       // cells of one x row of the tile
   __syncthreads();
@@ -1406,9 +1481,11 @@ __global__ void __launch_bounds__(256)
               anyz = anyz || tz[k] >= 0;
             }
             if (!(anyx && anyy && anyz)) continue;
-            float pay[C], wx[ORDER], wy[ORDER], wz[ORDER];
+            float pay[CT], wx[ORDER], wy[ORDER], wz[ORDER];
 #pragma unroll
             for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
+            // (the particle's rho_p |v_p|^2, once per record: it takes the same weight product as the four channels)
+            if constexpr (M2) pay[C] = second_moment_term(pay[0], pay[1], pay[2], pay[3]);
             assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
             assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
             assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
@@ -1424,7 +1501,7 @@ __global__ void __launch_bounds__(256)
                   const float wt = wx[kx] * wy[ky] * wz[kz];      // (the product order of assign_expand_kernel)
                   const int at = (tx[kx] * b.by + ty[ky]) * b.bz + tz[kz];
 #pragma unroll
-                  for (int c = 0; c < C; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
+                  for (int c = 0; c < CT; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
                 }
               }
             }
@@ -1454,12 +1531,18 @@ __global__ void __launch_bounds__(256)
         float4* t3 = reinterpret_cast<float4*>(tile + 3 * cells + loc);
         const float4 c0 = *t0, c1 = *t1, c2 = *t2, c3 = *t3;
         *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
+        float4 c4 = zero4;                       // the second moment (M2 only: a constant elsewhere)
+        if constexpr (M2) {
+          float4* t4 = reinterpret_cast<float4*>(tile + 4 * cells + loc);
+          c4 = *t4;
+          *t4 = zero4;
+        }
         if (inside) {
           float rx[4], ry[4], rz[4], rw[4];
-          cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx);
-          cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry);
-          cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz);
-          cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw);
+          cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
+          cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
+          cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
+          cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
 #pragma unroll
           for (int c = 0; c < NOUT; ++c) {
             vf4 q; q.x = rx[c]; q.y = ry[c]; q.z = rz[c]; q.w = rw[c];
@@ -1471,16 +1554,16 @@ __global__ void __launch_bounds__(256)
       for (int loc = loc_lo + (int)threadIdx.x; loc < loc_hi; loc += (int)blockDim.x) {
         const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
-        float v[C];
+        float v[CT];
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
+        for (int c = 0; c < CT; ++c) {
           v[c] = tile[c * cells + loc];
           tile[c * cells + loc] = 0.f;
         }
         if (gy >= N || gz >= N) continue;
         const long long cell = ((long long)(gx - x0) * N + gy) * N + gz;
         float r[4];
-        cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r);
+        cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, v[CT - 1]);
 #pragma unroll
         for (int c = 0; c < NOUT; ++c) __builtin_nontemporal_store(r[c], out + c * plane + cell);
       }
@@ -1624,6 +1707,8 @@ int deposit_assign_field_run(vps_ctx* ctx, const void* pos_v, const float* vel, 
   const F* pos = reinterpret_cast<const F*>(pos_v);
   const int xlo = x0 - (ORDER - 1);
   const int span = nx + ORDER - 1 >= N ? 0x7fffffff : nx + ORDER - 1;     // (the whole ring: every particle passes)
+  const size_t lds = tile_bytes(4, b.cells, quantity);       // (five channels for the second-moment quantities)
+  if (int rcl = check_second_moment_tile(ctx, quantity, lds)) return rcl;      // before anything is enqueued
   const int rc = assign_sort(ctx, AssignRhovPayload<F, ORDER>{pos, vel, rho, lcell},
                              [&](auto k) { return AssignSlabKeyOf<F, decltype(k), ORDER>{pos, lcell, (double)N, b, xlo, span}; },
                              np, p, work);
@@ -1634,19 +1719,21 @@ int deposit_assign_field_run(vps_ctx* ctx, const void* pos_v, const float* vel, 
     const int ix_lo = x0 / b.bx, ix_hi = (x0 + nx - 1) / b.bx;
     const long long per_x = (long long)b.nby * b.nbz;
     const long long first = ix_lo * per_x, nbricks = (ix_hi - ix_lo + 1) * per_x;
-    const size_t lds = (size_t)4 * b.cells * sizeof(float);
     long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
     long long grid_wg = (long long)ctx->num_cu * per_cu;
     if (grid_wg > nbricks) grid_wg = nbricks;
-    const int rcq = dispatch_quantity(quantity, [&](auto q) {
-      hipLaunchKernelGGL((assign_field_kernel<ORDER, decltype(q)::value>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+    const int rcq = dispatch_quantity<true>(quantity, [&](auto q) -> int {
+      auto kern = assign_field_kernel<ORDER, decltype(q)::value>;
+      if (lds > 64 * 1024)
+        VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
                          reinterpret_cast<const unsigned*>(work + p.l.records), reinterpret_cast<const unsigned*>(work + p.l.start),
                          b, first, nbricks, x0, nx, flags, brick_par(ctx, decltype(q)::value, vol), fields);
       return VPS_OK;
     });
-    if (rcq) return vps_fail(ctx, rcq, "vps_deposit_field: quantity %d", quantity);
+    if (rcq) return rcq == VPS_ERR_HIP ? rcq : vps_fail(ctx, rcq, "vps_deposit_field: quantity %d", quantity);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;
@@ -1721,6 +1808,9 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   if (rc) return rc;
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
+  if (vps_quantity_second_moment(quantity) && (flags & (VPS_FLAG_REFERENCE_MOMENTUM_BUG | VPS_FLAG_INPUT_IS_VM)))
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d (%s) takes neither VPS_FLAG_REFERENCE_MOMENTUM_BUG nor VPS_FLAG_INPUT_IS_VM",
+                    quantity, vps_second_moment_name(quantity));
   if (flags & VPS_FLAG_INPUT_IS_VM) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_INPUT_IS_VM is meaningless here");
   if (!fields_dev || !work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: null buffer");
@@ -1742,8 +1832,9 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
 
 int vps_deposit_fft_zy_supported(vps_ctx* ctx, int N, int quantity) {
   if (!ctx) return 0;
-  // (VPS_VM is four fields of two kinds: not a pencil launch)
-  return vps_quantity_valid(quantity) && quantity != VPS_VM && vps_pencil_supported(ctx, N) ? 1 : 0;
+  // (VPS_VM is four fields of two kinds: not a pencil launch; the second-moment quantities need a fifth tile channel, which the
+  //  pencil kernel does not have)
+  return vps_quantity_valid(quantity) && quantity != VPS_VM && !vps_quantity_second_moment(quantity) && vps_pencil_supported(ctx, N) ? 1 : 0;
 }
 
 size_t vps_deposit_fft_zy_workspace_bytes(int64_t np, int N, int nx) {
@@ -1902,6 +1993,7 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   int rc = check_deposit_args(ctx, "vps_deposit_fft_zy", np, N, Lbox, x0, nx);
   if (rc) return rc;
   if ((rc = refuse_assign_flags(ctx, "vps_deposit_fft_zy", flags))) return rc;
+  if ((rc = vps_refuse_second_moment(ctx, "vps_deposit_fft_zy", quantity, "the pencil kernel has no fifth channel"))) return rc;
   if (!vps_deposit_fft_zy_supported(ctx, N, quantity))
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_fft_zy: N=%d quantity=%d not supported by the fused path", N, quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_fft_zy", quantity, flags))) return rc;
@@ -2032,6 +2124,7 @@ int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, c
                           int64_t ncell, float* out_dev) {
   VPS_ENTER(ctx);
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (int rc = vps_refuse_second_moment(ctx, "vps_field_algebra", quantity, "a 4-channel grid does not hold a second moment")) return rc;
   if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;
   if (int rc = refuse_assign_flags(ctx, "vps_field_algebra", flags)) return rc;
   if (ncell < 0 || (ncell & 3)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: ncell must be a multiple of 4");

@@ -1942,7 +1942,8 @@ static int nn_resample_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
 // two differ in the last bit for some alpha, and each route keeps its own); alpha for the density.
 static NnEmit nn_emit_of(const vps_ctx* ctx, int quantity, int flags, double Lcell) {
   static const int forms[] = {NN_VELOCITY, NN_MOMENTUM, NN_ENERGY, NN_VM, NN_WEIGHTED, NN_DENSITY, NN_LOGDENS};   // by vps_quantity
-  static_assert(sizeof(forms) / sizeof(forms[0]) == VPS_LOG_DENSITY + 1, "one form per quantity code");
+  // (the second-moment codes above VPS_LOG_DENSITY never arrive: vps_nn_resample_quantity refuses them)
+  static_assert(sizeof(forms) / sizeof(forms[0]) == VPS_LOG_DENSITY + 1, "one form per quantity code the NN route takes");
   const int form = (quantity == VPS_MOMENTUM && (flags & VPS_FLAG_REFERENCE_MOMENTUM_BUG)) ? (int)NN_MOMBUG : forms[quantity];
   if (quantity == VPS_WEIGHTED_VELOCITY) return NnEmit{(float)(ctx->weight_alpha - 1.0), form};
   if (quantity == VPS_DENSITY) return NnEmit{(float)ctx->weight_alpha, form};
@@ -1965,6 +1966,7 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
   VPS_ENTER(ctx);
   if (!(Lcell > 0) || !out_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: bad Lcell / null output");
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: quantity %d", quantity);
+  if (int rc = vps_refuse_second_moment(ctx, "vps_nn_resample_quantity", quantity, "one nearest particle has no dispersion")) return rc;
   if (flags & VPS_FLAG_ASSIGN_MASK)   // (vps_deposit_field's: silently ignored here, the caller would get the NN field)
     return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: VPS_FLAG_ASSIGN is taken by vps_deposit_field only (flags 0x%x)", flags);
   if (int rc = vps_check_weighted(ctx, "vps_nn_resample_quantity", quantity, flags)) return rc;

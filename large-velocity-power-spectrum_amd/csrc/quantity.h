@@ -1,15 +1,21 @@
 // What a quantity (include/vps_hip.h: vps_quantity) is, once: its channels, whether it is a scalar of rho, whether it needs the
 // exponent of vps_set_density_weight -- and the two functions of rho that the density-weighted velocity and the scalar density
 // quantities are made of.  Shared by the brick / grid epilogues (deposit.hip), the NN emit (nn.hip) and the pencil kernel
-// (fft_pencil.h).  A new quantity starts here: its code in these four helpers, then its per-cell body in deposit.hip's cell_quantity.
+// (fft_pencil.h).  A new quantity starts here: its code in these five helpers, then its per-cell body in deposit.hip's cell_quantity.
 // Not part of the ABI.
 #pragma once
 #include "../../include/vps_hip.h"
 
-constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_LOG_DENSITY; }
+constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_DISPERSION; }
 // one output field, made from rho alone (channel 3 of [rho v, rho])
 constexpr bool vps_quantity_scalar_rho(int q) { return q == VPS_DENSITY || q == VPS_LOG_DENSITY; }
-constexpr int vps_quantity_channels(int q) { return q == VPS_VM ? 4 : (q == VPS_ENERGY || vps_quantity_scalar_rho(q)) ? 1 : 3; }
+// one output field that needs the second moment S2 = sum w rho_p |v_p|^2 next to the four cell totals: a fifth tile channel in
+// the deposit kernels (vps_deposit_field), nothing a 4-channel grid, one nearest particle or the pencil kernel can give -- every
+// other entry point refuses these codes (vps_refuse_second_moment)
+constexpr bool vps_quantity_second_moment(int q) { return q >= VPS_TOTAL_ENERGY && q <= VPS_DISPERSION; }
+constexpr int vps_quantity_channels(int q) {
+  return q == VPS_VM ? 4 : (q == VPS_ENERGY || vps_quantity_scalar_rho(q) || vps_quantity_second_moment(q)) ? 1 : 3;
+}
 // reads the context's alpha: VPS_ERR_ARG where it was never set (api.hip: vps_check_weighted)
 constexpr bool vps_quantity_needs_alpha(int q) { return q == VPS_WEIGHTED_VELOCITY || q == VPS_DENSITY; }
 

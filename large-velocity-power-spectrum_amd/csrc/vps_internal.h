@@ -96,6 +96,11 @@ double vps_option(const char* name, double dflt);
 // The scalar density quantities go through the same check: VPS_DENSITY needs the exponent too, and VPS_DENSITY /
 // VPS_LOG_DENSITY take none of VPS_FLAG_COMPONENTS, VPS_FLAG_SHARE_ENERGY, VPS_FLAG_REFERENCE_MOMENTUM_BUG.
 int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags);
+// The second-moment quantities (VPS_TOTAL_ENERGY, VPS_SUBGRID_ENERGY, VPS_DISPERSION) are formed by vps_deposit_field alone.
+// An entry point that cannot form them calls this first: VPS_ERR_ARG with the quantity's name, its number and `why`, before
+// anything is enqueued; VPS_OK for every other code.
+int vps_refuse_second_moment(vps_ctx* ctx, const char* who, int quantity, const char* why);
+const char* vps_second_moment_name(int quantity);
 
 // Every entry point of the C ABI runs with the context's device current and restores the caller's
 // on return: the library allocates (tables, partial sums, lattice axes) and launches on streams

@@ -31,6 +31,7 @@ MAXNBOX = 500
 LTOT = 1
 remove_bulk_velocity = True
 GRIDDINGS = ("nn", "ngp", "cic", "tsc")
+SECOND_MOMENT = ("total_energy", "subgrid_energy", "dispersion")      # vpower.device.SECOND_MOMENT_QUANTITIES: deposits only
 
 
 def build_parser():
@@ -48,8 +49,11 @@ def build_parser():
                         "Pk_compressive.txt and Pk_solenoidal.txt, in Pk.txt's format.")
     p.add_argument("--quantity", type=str, default="velocity", metavar="NAME",
                    help="What to take the spectrum of: velocity (default: the reference's raw nearest-neighbour velocity, Pk.txt "
-                        "unchanged), momentum, energy, weighted_velocity, rho13_velocity, rho12_velocity, density, log_density "
-                        "(vpower.device.resolve_quantity).  Every quantity but velocity needs PartType0/Density in the snapshot.")
+                        "unchanged), momentum, energy, weighted_velocity, rho13_velocity, rho12_velocity, density, log_density, "
+                        "total_energy, subgrid_energy, dispersion (vpower.device.resolve_quantity; the last three are the "
+                        "kinetic energy of a cell's particles, its part the gridded mean velocity does not resolve, and the velocity "
+                        "dispersion: --gridding ngp, cic or tsc only).  Every quantity but velocity needs PartType0/Density in the "
+                        "snapshot.")
     p.add_argument("--density-weight", type=float, default=None, metavar="ALPHA",
                    help="Exponent alpha of --quantity weighted_velocity (rho^alpha v) or density (rho^alpha; default 1).")
     p.add_argument("--gridding", type=str, default="nn", choices=GRIDDINGS,
@@ -65,6 +69,9 @@ def check_gridding(parser, args):
     """--deconvolve needs a mass-assignment window: refused (parser.error) with the nearest-neighbour gridding."""
     if args.deconvolve and args.gridding == "nn":
         parser.error("--deconvolve divides by the window of a mass assignment: pass --gridding ngp, cic or tsc")
+    if args.quantity in SECOND_MOMENT and args.gridding == "nn":
+        parser.error("--quantity %s is made of the second moment of a cell's particles, and one nearest particle has none: "
+                     "pass --gridding ngp, cic or tsc" % args.quantity)
     return args
 
 
@@ -172,6 +179,9 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
         raise ValueError("deconvolve needs a mass-assignment gridding (ngp, cic, tsc), not the nearest-neighbour resampling")
     if gridding != "nn" and density is None:
         raise Exception("every deposit gridding needs the particle densities (the velocity is sum rho v / sum rho)")
+    if gridding == "nn" and quantity is not None and device.needs_second_moment(quantity):
+        raise ValueError("the second-moment quantities (total_energy, subgrid_energy, dispersion) need a mass-assignment gridding "
+                         "(ngp, cic, tsc): one nearest particle has no dispersion")
     k = kernels if kernels is not None else device.default_kernels()
     pipe = device.PowerPipeline(ntot, ltot, kernels=k, comm=comm, flavour="script", deconvolve=gridding if deconvolve else None)
     lcell = ltot / ntot

@@ -29,14 +29,24 @@ import torch
 from . import _ffi
 
 VELOCITY, MOMENTUM, ENERGY, VM, WEIGHTED, DENSITY, LOG_DENSITY = 0, 1, 2, 3, 4, 5, 6
+# the second-moment scalars of a cell's contributions (vps_deposit_field alone forms them: NGP / CIC / TSC deposits), with
+# S2 = sum w rho_p |v_p|^2, P = sum w rho v, R = sum w rho: vol S2, vol (S2 - |P|^2 / R), (S2 - |P|^2 / R) / R
+TOTAL_ENERGY, SUBGRID_ENERGY, DISPERSION = 7, 8, 9
+SECOND_MOMENT_QUANTITIES = {"total_energy": TOTAL_ENERGY, "subgrid_energy": SUBGRID_ENERGY, "dispersion": DISPERSION}
 QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED,
-            "density": DENSITY, "log_density": LOG_DENSITY}
+            "density": DENSITY, "log_density": LOG_DENSITY, **SECOND_MOMENT_QUANTITIES}
 FLAG_REFERENCE_MOMENTUM_BUG = 1
 FLAG_INPUT_IS_VM = 2
 FLAG_REUSE_SORT = 4
 FLAG_SHARE_ENERGY = 8
-NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3, DENSITY: 1, LOG_DENSITY: 1}      # output channels of a quantity
-SCALAR_QUANTITIES = ("energy", "density", "log_density")      # one field each: dealt out and transformed as one unit
+NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3, DENSITY: 1, LOG_DENSITY: 1,      # output channels of a quantity
+         TOTAL_ENERGY: 1, SUBGRID_ENERGY: 1, DISPERSION: 1}                                        # (csrc/quantity.h: vps_quantity_channels)
+SCALAR_QUANTITIES = ("energy", "density", "log_density") + tuple(SECOND_MOMENT_QUANTITIES)      # one field each: dealt out and transformed as one unit
+
+
+def needs_second_moment(quantity):
+    """Whether a quantity (name or code) is one of the second-moment scalars, which only a particle deposit can form."""
+    return quantity in SECOND_MOMENT_QUANTITIES if isinstance(quantity, str) else int(quantity) in SECOND_MOMENT_QUANTITIES.values()
 
 
 class WeightedVelocity(int):
@@ -102,7 +112,8 @@ VECTOR_QUANTITIES = ("velocity", "momentum", "weighted_velocity") + tuple(WEIGHT
 
 def resolve_quantity(quantity, density_weight=None, supported=None):
     """(name, code) of a quantity name of BoxField.spctrm: name is 'velocity' | 'momentum' | 'energy' | 'weighted_velocity' |
-    'density' | 'log_density', code the library's (a WeightedVelocity / Density carrying alpha for those two).
+    'density' | 'log_density' | 'total_energy' | 'subgrid_energy' | 'dispersion', code the library's (a WeightedVelocity /
+    Density carrying alpha for those two).
     'weighted_velocity' needs density_weight = alpha (finite); 'rho13_velocity' / 'rho12_velocity' are alpha = 1/3 and 1/2;
     'density' is rho^alpha with density_weight = alpha, the plain density (alpha = 1) without; density_weight with any other
     name is an error.
@@ -411,7 +422,9 @@ class HipKernels:
     def deposit_field(self, pos, vel, rho, N, Lbox, x0, nx, quantity, flags=0, out=None, assignment="ngp"):
         """Fused deposit of [rho v, rho] + field algebra -> [ncomp, nx, N, N] float32.  assignment = "cic" / "tsc": the same
         fields of the CIC / TSC cell totals on the slab (VPS_FLAG_ASSIGN: one sort record per particle, the quantity formed in
-        the owner brick's epilogue), from a workspace of its own sized by vps_deposit_assign_workspace_bytes."""
+        the owner brick's epilogue), from a workspace of its own sized by vps_deposit_assign_workspace_bytes.
+        TOTAL_ENERGY / SUBGRID_ENERGY / DISPERSION -> [1, nx, N, N]: the scalars of the cell's second moment
+        sum w rho_p |v_p|^2 (a fifth channel of the brick's LDS tile; the same records and workspaces), with every assignment."""
         assign = FLAG_ASSIGN(assignment)
         if int(flags) & FLAG_ASSIGN_MASK:
             # (the workspace below is sized from `assignment`: bits arriving in `flags` would run CIC / TSC in the NGP workspace)

@@ -393,13 +393,55 @@ class BoxField:
             return [work[0]]
         raise Exception("""Unrecognized physical quantity name.
         Supported: 'velocity', 'momentum', 'energy', 'weighted_velocity' (with density_weight=alpha), 'rho13_velocity',
-        'rho12_velocity', 'density' (density_weight=alpha optional), 'log_density'.""")
+        'rho12_velocity', 'density' (density_weight=alpha optional), 'log_density'; on particle-backed fields also 'total_energy',
+        'subgrid_energy', 'dispersion'.""")
 
     def _assigned_fields(self, k, src, quantity, qcode):
-        """The fields of a quantity of a lazy CIC / TSC field: one fused deposit of the particles src = (pos, vel, rho)."""
+        """The fields of a quantity of a lazy particle-backed field (CIC / TSC; NGP for the second-moment quantities): one fused
+        deposit of the particles src = (pos, vel, rho)."""
         flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
-        f = k.deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, qcode, flags, assignment=self.assignment)
+        f = k.deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, qcode, flags,
+                            assignment=getattr(self, "assignment", "ngp"))
         return [f[i] for i in range(f.shape[0])]
+
+    def _second_moment_source(self, quantity):
+        """The particles (pos, vel, rho) a second-moment quantity is deposited from, or an Exception that names the quantity:
+        sum rho_p |v_p|^2 over a cell's particles is not a function of the four gridded channels, so only a particle-backed
+        field (`GasParticles.deposit_to_field(N)`, or `(N, assignment=..., method="fused")`) whose grids have not been built
+        yet can form it.  Raised before anything touches the device."""
+        src = getattr(self, "_src", None)
+        if src is not None:
+            return src
+        if getattr(self, "_nn_src", None) is not None or hasattr(self, "_nn_spectra"):
+            why = "a neighbour-backed field (ann_interp_to_field) takes one nearest particle per cell, which has no dispersion"
+        else:
+            why = ("a field of four gridded channels (built from arrays, or already materialised) does not hold the second moment "
+                   "sum rho |v|^2 of its cells' particles")
+        raise Exception("quantity %r needs the particles behind the field -- GasParticles.deposit_to_field(N) or "
+                        "deposit_to_field(N, assignment='cic' | 'tsc', method='fused'): %s" % (quantity, why))
+
+    def _second_moment_grid(self, quantity):
+        src = self._second_moment_source(quantity)
+        k = _kernels()
+        f = self._assigned_fields(k, src, quantity, _dev.QUANTITY[quantity])
+        return f[0].cpu().numpy().astype(np.float64)
+
+    def total_energy(self) -> np.ndarray:
+        """(N,N,N) float64 real-space grid of E_tot = Lcell^3 sum w rho_p |v_p|^2 over the contributions to a cell (weight w of
+        the field's mass assignment; no factor 1/2, as `kinetic_energy_power`'s E): the kinetic energy of the cell's particles.
+        Its sum over the cells is Lcell^3 sum_p rho_p |v_p|^2 whatever the assignment.  Particle-backed fields only (extension)."""
+        return self._second_moment_grid("total_energy")
+
+    def subgrid_energy(self) -> np.ndarray:
+        """(N,N,N) float64 real-space grid of E_sub = E_tot - E, E = mass |v|^2 of the cell's mean velocity: the kinetic energy
+        the gridded field does not resolve, >= 0, 0 in empty cells and in cells with one NGP particle.  Particle-backed fields
+        only (extension)."""
+        return self._second_moment_grid("subgrid_energy")
+
+    def dispersion(self) -> np.ndarray:
+        """(N,N,N) float64 real-space grid of sigma^2 = <|v|^2> - |<v>|^2, the density-weighted velocity dispersion of the
+        cell's contributions, >= 0 and 0 in empty cells.  Particle-backed fields only (extension)."""
+        return self._second_moment_grid("dispersion")
 
     def _power(self, quantity):
         k = _kernels()
@@ -449,14 +491,23 @@ class BoxField:
         the density itself, which takes no transcendental at all) and s = ln rho in the caller's units, on every kind of field;
         s = 0 in empty cells.  A reference density rho0 in ln(rho / rho0) only moves the k = 0 mode, which no shell holds, as
         long as no cell is empty; an empty cell counts as rho = 1, so with a sparse NGP grid rescale the densities or use the
-        nearest-neighbour route (`ann_interp_to_field`).  'log_density' takes no density_weight."""
+        nearest-neighbour route (`ann_interp_to_field`).  'log_density' takes no density_weight.
+        'total_energy', 'subgrid_energy' and 'dispersion' (extension): the SCALAR fields of the second moment of a cell's
+        contributions, S2 = sum w rho_p |v_p|^2 -- E_tot = Lcell^3 S2, E_sub = E_tot - E with E the field of 'energy' (the kinetic
+        energy the gridded mean velocity does not resolve; >= 0) and sigma^2 = <|v|^2> - |<v>|^2; 0 in empty cells.  Only a
+        particle-backed field whose grids have not been built can form them (`GasParticles.deposit_to_field(N)`, or with
+        assignment='cic' | 'tsc' and method='fused'): one deposit with a fifth LDS tile channel, then the transform of any
+        gridded scalar; every other field raises an Exception naming the quantity.  `deconvolve` as for the other scalars."""
         quantity, qcode = _dev.resolve_quantity(quantity, density_weight)
+        second_moment = _dev.needs_second_moment(qcode)
+        if second_moment:
+            self._second_moment_source(quantity)     # (raises by name on a field without particles, before any device work)
         k = _kernels()
         pipe = _dev.PowerPipeline(self.Nsize, self.Lbox, kernels=k, comm=_dev.SlabComm(enabled=False),
                                   flavour="library", kmin=kmin, kmax=kmax, kres=kres,
                                   deconvolve=(getattr(self, "assignment", "ngp") if deconvolve else None))
         src = getattr(self, "_src", None)
-        if src is not None and getattr(self, "assignment", "ngp") != "ngp":
+        if src is not None and (second_moment or getattr(self, "assignment", "ngp") != "ngp"):
             # particle-backed CIC / TSC field (deposit_to_field(..., method="fused")): particles -> the fields of this quantity
             return PowerSpectrum(pipe.spectrum(self._assigned_fields(k, src, quantity, qcode)))
         if src is not None and k.fused_supported(self.Nsize, qcode):
