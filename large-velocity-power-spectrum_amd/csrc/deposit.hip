@@ -10,7 +10,7 @@
 //                fused path) by a two-level LDS bucket sort -- chunk histograms, one scan, LDS-staged
 //                runs, one workgroup per coarse group (bucket_sort.h, shared with the NN cell list).  No global
 //                atomic per particle, no random 20-byte writes.  A one-atomic-per-particle ranking
-//                (brick_rank_kernel / brick_scatter_kernel) remains for bucket counts or key ranges
+//                (rank_kernel / rank_scatter_kernel) remains for bucket counts or key ranges
 //                the sort does not cover.
 //   2. buckets : one workgroup per bucket adds its records into an LDS tile and then either streams
 //                the WHOLE tile out with full-width coalesced stores (rows of bz cells), applying the
@@ -137,61 +137,28 @@ __device__ __forceinline__ bool locate(const F* __restrict__ pos, long long i, F
   return true;
 }
 
-// Pass 1: one returning atomic per particle gives both the brick histogram and the
-// particle's rank inside its brick.  key = brick * cells + cell-in-brick (0xffff.. = outside).
-template <typename F>
-__global__ void __launch_bounds__(256)
-    brick_rank_kernel(const F* __restrict__ pos, long long np, F lcell, F nsize, Bricks b,
-                      unsigned* __restrict__ count, unsigned long long* __restrict__ keys,
-                      unsigned* __restrict__ ranks) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  unsigned brick, loc;
-  if (locate<F>(pos, i, lcell, nsize, b, brick, loc)) {
-    ranks[i] = atomicAdd(&count[brick], 1u);
-    keys[i] = (unsigned long long)brick * (unsigned)b.cells + loc;
-  } else {
-    keys[i] = ~0ull;
-  }
+// brick id -> (ix, iy, iz): the brick's first cell is (ix bx, iy by, iz bz)
+__device__ __forceinline__ void brick_index(const Bricks& b, long long brick, int& ix, int& iy, int& iz) {
+  iz = (int)(brick % b.nbz);
+  iy = (int)((brick / b.nbz) % b.nby);
+  ix = (int)(brick / ((long long)b.nbz * b.nby));
 }
 
-// Pass 2 (after the scan): record = {loc, payload[C]} as (C+1) 32-bit words goes to slot
-// start[brick] + rank.  RHOV: payload is built from velocity and density on the fly
-// ([rho vx, rho vy, rho vz, rho], interp.py:199-213).
-template <int C, bool RHOV>
-__global__ void __launch_bounds__(256)
-    brick_scatter_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ ranks,
-                         const float* __restrict__ payload, const float* __restrict__ rho, long long np,
-                         unsigned cells, const unsigned* __restrict__ start,
-                         unsigned* __restrict__ records) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  const unsigned long long key = keys[i];
-  if (key == ~0ull) return;
-  const unsigned brick = (unsigned)(key / cells), loc = (unsigned)(key % cells);
-  float val[C];
-  if constexpr (RHOV) {
-    static_assert(C == 4, "rho*v payload has four channels");
-    const float r = rho[i];
-    val[0] = payload[i * 3 + 0] * r;
-    val[1] = payload[i * 3 + 1] * r;
-    val[2] = payload[i * 3 + 2] * r;
-    val[3] = r;
-  } else if constexpr (C == 4) {
-    const float4 p4 = *reinterpret_cast<const float4*>(payload + i * 4);
-    val[0] = p4.x; val[1] = p4.y; val[2] = p4.z; val[3] = p4.w;
+// cell-in-brick word -> (lx, ly, lz), by shifts where by and bz are powers of two (SHIFTS = false: the scalar stream-out of the
+// shapes that are no multiple of four divides, as it always did)
+template <bool SHIFTS = true>
+__device__ __forceinline__ void brick_cell(const Bricks& b, int loc, int& lx, int& ly, int& lz) {
+  if (SHIFTS && b.pow2) {
+    lz = loc & (b.bz - 1);
+    ly = (loc >> b.sz) & (b.by - 1);
+    lx = loc >> (b.sz + b.sy);
   } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) val[c] = payload[i * C + c];
+    lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
   }
-  unsigned* rec = records + (size_t)(start[brick] + ranks[i]) * (C + 1);
-  rec[0] = loc;
-#pragma unroll
-  for (int c = 0; c < C; ++c) rec[1 + c] = __float_as_uint(val[c]);
 }
 
 // ---- the two-level bucket sort (bucket_sort.h) as the deposit uses it ----------------------------------------------------
-// Records {cell-in-bucket, payload[C]} grouped by bucket + start[], the same as rank -> scan -> scatter above gives, from the
+// Records {cell-in-bucket, payload[C]} grouped by bucket + start[], the same as rank -> scan -> scatter below gives, from the
 // shared kernels: two particles per thread in level 1, final records that keep their cell-in-bucket word.
 #ifndef VPS_SORT_ITEMS
 #define VPS_SORT_ITEMS 2
@@ -337,6 +304,7 @@ __global__ void __launch_bounds__(COMPACT_THREADS)
       if ((long long)(blk_base + at) < cap) ckeys[blk_base + at] = sort_invalid<K>();
 }
 
+// RHOV: the payload is built from velocity and density on the fly ([rho vx, rho vy, rho vz, rho], interp.py:199-213)
 template <int C, bool RHOV>
 __device__ __forceinline__ void load_payload(const float* __restrict__ payload, const float* __restrict__ rho,
                                              long long i, float val[C]) {
@@ -363,6 +331,38 @@ struct DepPayload {
   const float* __restrict__ rho;
   __device__ __forceinline__ void load(long long i, float val[C_]) const { load_payload<C_, RHOV>(payload, rho, i, val); }
 };
+
+// One-atomic-per-particle ranking with the key and payload functors of the sort (option sort_atomic, or a geometry the two-level
+// sort does not cover).  Pass 1: one returning atomic per particle gives both the bucket histogram and the particle's rank inside
+// its bucket; key = bucket * cells + cell-in-bucket (0xffff.. = nowhere).
+template <typename KeyOf>
+__global__ void __launch_bounds__(256)
+    rank_kernel(KeyOf key_of, long long np, unsigned cells, unsigned* __restrict__ count,
+                unsigned long long* __restrict__ keys, unsigned* __restrict__ ranks) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  const unsigned long long key = key_of(i);
+  keys[i] = key;
+  if (key != ~0ull) ranks[i] = atomicAdd(&count[key / cells], 1u);
+}
+
+// Pass 2 (after the scan): record = {loc, payload[C]} as (C+1) 32-bit words goes to slot start[bucket] + rank.
+template <typename Payload>
+__global__ void __launch_bounds__(256)
+    rank_scatter_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ ranks, Payload pay,
+                        long long np, unsigned cells, const unsigned* __restrict__ start, unsigned* __restrict__ records) {
+  constexpr int C = Payload::C;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  const unsigned long long key = keys[i];
+  if (key == ~0ull) return;
+  float val[C];
+  pay.load(i, val);
+  unsigned* rec = records + (size_t)(start[key / cells] + ranks[i]) * (C + 1);
+  rec[0] = (unsigned)(key % cells);
+#pragma unroll
+  for (int c = 0; c < C; ++c) rec[1 + c] = __float_as_uint(val[c]);
+}
 
 // Epilogue of the brick kernel: what is written for a cell from its C accumulated channels.
 //   EPI_RAW      : the C channels as they are (deposit_to_grid)
@@ -510,6 +510,96 @@ int check_second_moment_tile(vps_ctx* ctx, int quantity, size_t lds) {
   return VPS_OK;
 }
 
+// ---- the stream-out of an LDS tile [CT][cells], shared by the brick kernels of every route -------------------------------------
+// What the kernel's epilogue is made of, at compile time: C record channels, CT tile channels (the second-moment quantities keep
+// S2 = sum w rho_p |v_p|^2 in a channel of its own behind the C record channels: the records stay [rho v, rho]), NOUT written.
+template <int C, int EPI, int QUANT>
+struct TileOut {
+  static constexpr bool M2 = EPI == EPI_ALGEBRA && vps_quantity_second_moment(QUANT);
+  static constexpr int CT = M2 ? C + 1 : C;
+  static constexpr int NOUT = (EPI == EPI_RAW) ? C : vps_quantity_channels(QUANT);
+  static_assert(EPI == EPI_RAW || C == 4, "quantities are formed from [rho v, rho] records");
+};
+// (algebra_cell reads the flags at run time, as it always did; the quantities of rho see their constant 0)
+template <int QUANT>
+__device__ __forceinline__ int tile_cflags(int flags) {
+  return (vps_quantity_needs_alpha(QUANT) || vps_quantity_scalar_rho(QUANT)) ? 0 : flags;
+}
+typedef float vf4 __attribute__((ext_vector_type(4)));
+
+// Four consecutive cells from `loc` on: their CT channels are read and zeroed; if the quad is inside the grid its NOUT fields go
+// to out[c * plane + cell].  The quantity fields leave by streaming stores (the grid is written once; the cache should keep the
+// records: -33 %).  The raw channels do so with STREAM only: the NGP deposit has always written them with plain stores, the
+// direct one with streaming stores, and each keeps its own.
+template <int C, int EPI, int QUANT, bool STREAM>
+__device__ __forceinline__ void tile_out4(float* tile, int cells, int loc, bool inside, int cflags, CellPar cpar,
+                                          float* __restrict__ out, long long plane, long long cell) {
+  typedef TileOut<C, EPI, QUANT> T;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (EPI == EPI_RAW) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float4* t = reinterpret_cast<float4*>(tile + c * cells + loc);
+      const float4 val = *t;
+      *t = zero4;
+      if (inside) {
+        if constexpr (STREAM) {
+          vf4 q; q.x = val.x; q.y = val.y; q.z = val.z; q.w = val.w;
+          __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(out + c * plane + cell));
+        } else {
+          *reinterpret_cast<float4*>(out + c * plane + cell) = val;
+        }
+      }
+    }
+  } else {
+    float4* t0 = reinterpret_cast<float4*>(tile + loc);
+    float4* t1 = reinterpret_cast<float4*>(tile + cells + loc);
+    float4* t2 = reinterpret_cast<float4*>(tile + 2 * cells + loc);
+    float4* t3 = reinterpret_cast<float4*>(tile + 3 * cells + loc);
+    const float4 c0 = *t0, c1 = *t1, c2 = *t2, c3 = *t3;
+    *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
+    float4 c4 = zero4;                       // the second moment (M2 only: a constant elsewhere)
+    if constexpr (T::M2) {
+      float4* t4 = reinterpret_cast<float4*>(tile + 4 * cells + loc);
+      c4 = *t4;
+      *t4 = zero4;
+    }
+    if (inside) {
+      float rx[4], ry[4], rz[4], rw[4];
+      cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
+      cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
+      cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
+      cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
+#pragma unroll
+      for (int c = 0; c < T::NOUT; ++c) {
+        vf4 q; q.x = rx[c]; q.y = ry[c]; q.z = rz[c]; q.w = rw[c];
+        __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(out + c * plane + cell));
+      }
+    }
+  }
+}
+
+// ... and its scalar twin for the bricks and grids that are no multiple of four: one cell.  STREAM: every store of it.
+template <int C, int EPI, int QUANT, bool STREAM>
+__device__ __forceinline__ void tile_out1(float* tile, int cells, int loc, bool inside, int cflags, CellPar cpar,
+                                          float* __restrict__ out, long long plane, long long cell) {
+  typedef TileOut<C, EPI, QUANT> T;
+  float v[T::CT], r[4];
+#pragma unroll
+  for (int c = 0; c < T::CT; ++c) {
+    v[c] = tile[c * cells + loc];
+    tile[c * cells + loc] = 0.f;
+  }
+  if (!inside) return;
+  if constexpr (EPI == EPI_ALGEBRA) cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, T::M2 ? v[T::CT - 1] : 0.f);
+#pragma unroll
+  for (int c = 0; c < T::NOUT; ++c) {
+    const float val = EPI == EPI_ALGEBRA ? r[c] : v[c];
+    if constexpr (STREAM) __builtin_nontemporal_store(val, out + c * plane + cell);
+    else out[c * plane + cell] = val;
+  }
+}
+
 // QUANT is the (compile-time) quantity of the algebra epilogue; NOUT its channel count.  `par` is the ONE float that epilogue
 // reads (brick_par): the channels are [rho v, rho] cell totals, never [v, mass], so a quantity needs the cell volume or alpha,
 // not both.
@@ -518,18 +608,14 @@ __global__ void __launch_bounds__(256)
     brick_accumulate_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start,
                             Bricks b, long long nbricks, int flags, float par,
                             float* __restrict__ grid) {
-  constexpr int NOUT = (EPI == EPI_RAW) ? C : vps_quantity_channels(QUANT);
-  // (algebra_cell reads the flags at run time, as it always did; the quantities of rho see their constant 0)
-  const int cflags = (vps_quantity_needs_alpha(QUANT) || vps_quantity_scalar_rho(QUANT)) ? 0 : flags;
+  const int cflags = tile_cflags<QUANT>(flags);
   // One float, copied into both members: every quantity here reads exactly one of them.  QUANT < VPS_WEIGHTED_VELOCITY reads
   // par.vol (the volume) and never par.alpha; QUANT >= VPS_WEIGHTED_VELOCITY reads par.alpha and, with cflags = 0, never par.vol,
   // which is MEANINGLESS for them here (it holds alpha).  A two-float kernel argument would move this kernel's code.
   const CellPar cpar{par, par};
-  // The second-moment quantities (compile time: nothing of it exists in the other instantiations) keep S2 = sum rho_p |v_p|^2 in
-  // a channel of its own behind the C record channels: CT tile channels, the records stay [rho v, rho].
-  constexpr bool M2 = EPI == EPI_ALGEBRA && vps_quantity_second_moment(QUANT);
-  constexpr int CT = M2 ? C + 1 : C;
-  static_assert(!M2 || C == 4, "the second moment is formed from [rho v, rho] records");
+  // (the second-moment channel is compile time: nothing of it exists in the other instantiations)
+  constexpr bool M2 = TileOut<C, EPI, QUANT>::M2;
+  constexpr int CT = TileOut<C, EPI, QUANT>::CT;
   // Persistent workgroups walk the bricks: the streaming stores of one brick stay in flight
   // while the next bucket is being accumulated, and the tile is re-zeroed as it is read.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -568,83 +654,28 @@ __global__ void __launch_bounds__(256)
     }
     __syncthreads();
     // stream the tile out: rows of bz cells are contiguous in the grid
-    const int iz = (int)(brick % b.nbz), iy = (int)((brick / b.nbz) % b.nby);
-    const int ix = (int)(brick / ((long long)b.nbz * b.nby));
+    int ix, iy, iz;
+    brick_index(b, brick, ix, iy, iz);
     const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
     if (vec4) {
       const int q4 = cells / 4;
       for (int i = threadIdx.x; i < q4; i += blockDim.x) {
         const int loc = i * 4;
         int lz, ly, lx;
-        if (b.pow2) {
-          lz = loc & (b.bz - 1);
-          ly = (loc >> b.sz) & (b.by - 1);
-          lx = loc >> (b.sz + b.sy);
-        } else {
-          lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
-        }
+        brick_cell(b, loc, lx, ly, lz);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
         const bool inside = gx < b.nx && gy < b.N && gz < b.N;   // partial bricks at the slab edge
         const long long cell = ((long long)gx * b.N + gy) * b.N + gz;
-        const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (EPI == EPI_RAW) {
-#pragma unroll
-          for (int c = 0; c < C; ++c) {
-            float4* t = reinterpret_cast<float4*>(tile + c * cells + loc);
-            const float4 val = *t;
-            *t = zero4;
-            if (inside) *reinterpret_cast<float4*>(grid + c * plane + cell) = val;
-          }
-        } else {
-          float4* t0 = reinterpret_cast<float4*>(tile + loc);
-          float4* t1 = reinterpret_cast<float4*>(tile + cells + loc);
-          float4* t2 = reinterpret_cast<float4*>(tile + 2 * cells + loc);
-          float4* t3 = reinterpret_cast<float4*>(tile + 3 * cells + loc);
-          const float4 c0 = *t0, c1 = *t1, c2 = *t2, c3 = *t3;
-          *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
-          float4 c4 = zero4;                       // the second moment (M2 only: a constant elsewhere)
-          if constexpr (M2) {
-            float4* t4 = reinterpret_cast<float4*>(tile + 4 * cells + loc);
-            c4 = *t4;
-            *t4 = zero4;
-          }
-          if (inside) {
-            float rx[4], ry[4], rz[4], rw[4];
-            cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
-            cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
-            cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
-            cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
-#pragma unroll
-            for (int c = 0; c < NOUT; ++c)
-              {   // streaming store: the grid is written once; the cache should keep the records (-33 %)
-                typedef float vf4 __attribute__((ext_vector_type(4)));
-                vf4 q; q.x = rx[c]; q.y = ry[c]; q.z = rz[c]; q.w = rw[c];
-                __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(grid + c * plane + cell));
-              }
-          }
-        }
+        tile_out4<C, EPI, QUANT, false>(tile, cells, loc, inside, cflags, cpar, grid, plane, cell);
       }
     } else {
       for (int loc = threadIdx.x; loc < cells; loc += blockDim.x) {
-        const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
+        int lz, ly, lx;
+        brick_cell<false>(b, loc, lx, ly, lz);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
-        float v[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          v[c] = tile[c * cells + loc];
-          tile[c * cells + loc] = 0.f;
-        }
-        if (gx >= b.nx || gy >= b.N || gz >= b.N) continue;
+        const bool inside = gx < b.nx && gy < b.N && gz < b.N;
         const long long cell = ((long long)gx * b.N + gy) * b.N + gz;
-        if constexpr (EPI == EPI_RAW) {
-#pragma unroll
-          for (int c = 0; c < C; ++c) grid[c * plane + cell] = v[c];
-        } else {
-          float r[4];
-          cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, M2 ? v[CT - 1] : 0.f);
-#pragma unroll
-          for (int c = 0; c < NOUT; ++c) grid[c * plane + cell] = r[c];
-        }
+        tile_out1<C, EPI, QUANT, false>(tile, cells, loc, inside, cflags, cpar, grid, plane, cell);
       }
     }
     __syncthreads();   // tile is all zero again
@@ -898,106 +929,135 @@ DepLayout dep_layout(int64_t np, int C, const Bricks& b, int64_t np_cap = -1) {
   return l;
 }
 
-// particles -> records {cell-in-bucket, payload[C]} grouped by bucket + start[nbuckets + 1]
-template <typename F, int C, bool RHOV>
-int sort_into_buckets(vps_ctx* ctx, const F* pos, const float* payload, const float* rho, int64_t np, F lcell,
-                      F nsz, const Bricks& b, const DepLayout& l, char* work) {
+// a kernel whose dynamic LDS exceeds the 64 KiB every kernel may have is allowed its `lds` bytes first
+template <typename Kern>
+int raise_lds_limit(vps_ctx* ctx, Kern kern, size_t lds) {
+  if (lds > 64 * 1024)
+    VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return VPS_OK;
+}
+
+// persistent workgroups of a brick kernel with an LDS tile of `lds` bytes: what a CU holds of them (1 .. 8), at most one per brick
+unsigned brick_launch_grid(const vps_ctx* ctx, size_t lds, long long nbricks) {
+  long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
+  if (per_cu > 8) per_cu = 8;
+  if (per_cu < 1) per_cu = 1;
+  return (unsigned)std::min<long long>((long long)ctx->num_cu * per_cu, nbricks);
+}
+
+// The sort driver of every deposit route: n particles -> records {cell-in-bucket, payload[Pay::C]} grouped by bucket +
+// start[nbuckets + 1], in the workspace `l` lays out.  pay: the payload functor (DepPayload, AssignPayload); key_of(K{}): the key
+// functor for keys of type K (DepKeyOf, StoredKeyOf, AssignKeyOf).  The caller holds the launch timer.
+template <typename KeyMaker, typename Pay>
+int sort_records(vps_ctx* ctx, KeyMaker key_of, const Pay& pay, long long n, const DepLayout& l, char* work) {
+  constexpr int CR = Pay::C;
   unsigned* count = reinterpret_cast<unsigned*>(work + l.count);
   unsigned* start = reinterpret_cast<unsigned*>(work + l.start);
   unsigned* records = reinterpret_cast<unsigned*>(work + l.records);
-  vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
-  if (np == 0) {
+  const SortGeom& g = l.geom;
+  if (n == 0) {     // (nothing to sort: start[] is all zero)
     VPS_HIP_CHECK(ctx, hipMemsetAsync(start, 0, sizeof(unsigned) * (l.nbricks + 1), ctx->stream));
     return VPS_OK;
   }
   if (l.two_level) {
-    const SortGeom& g = l.geom;
     unsigned* table = reinterpret_cast<unsigned*>(work + l.table);
     unsigned* table_start = reinterpret_cast<unsigned*>(work + l.table_start);
     unsigned* table_tiles = reinterpret_cast<unsigned*>(work + l.table_tiles);
     unsigned* rec1 = reinterpret_cast<unsigned*>(work + l.rec1);
     const size_t lds1 = sort_hist_lds(g), lds2 = sort_fine_lds(g);
-    const size_t lds_staged = sort_staged_lds(g, C, SORT_ITEMS);
+    const size_t lds_staged = sort_staged_lds(g, CR, SORT_ITEMS);
     const bool staged = sort_staged() && lds_staged <= ctx->lds_per_cu;
-    if (l.recompute && !staged) return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "slab-sized sort workspace needs the LDS-staged scatter");
     auto level1 = [&](auto* keys) -> int {
       typedef typename std::remove_pointer<decltype(keys)>::type K;
-      long long n_sort = np;                   // particles the sort proper sees
-      const float* pay = payload;
-      if (l.recompute) {
-        // filter first: {key, [rho v, rho]} of the slab's particles, compact
-        if constexpr (RHOV) {
-          unsigned long long* counter = reinterpret_cast<unsigned long long*>(work + l.counter);
-          float4* cpay = reinterpret_cast<float4*>(work + l.cpay);
-          VPS_HIP_CHECK(ctx, hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
-          const long long nch = (np + (long long)COMPACT_THREADS * COMPACT_ITEMS - 1) / ((long long)COMPACT_THREADS * COMPACT_ITEMS);
-          const unsigned cgrid = (unsigned)std::min<long long>(std::min<long long>(nch, (long long)ctx->num_cu * 8), COMPACT_MAXGRID);
-          hipLaunchKernelGGL((slab_compact_kernel<F, K>), dim3(cgrid), dim3(COMPACT_THREADS), 0, ctx->stream, pos, payload, rho,
-                             (long long)np, lcell, nsz, b, g, keys, cpay, counter, l.cap_in);
-          unsigned long long reserved = 0;      // slots handed out: the slab's particles + at most one partly used block per workgroup
-          VPS_HIP_CHECK(ctx, hipMemcpyAsync(&reserved, counter, sizeof(reserved), hipMemcpyDeviceToHost, ctx->stream));
-          VPS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-          if ((long long)reserved > l.cap_in)
-            return vps_fail(ctx, VPS_ERR_ARG, "more particles lie inside the slab than the workspace was sized for (%lld; vps_count_in_slab)",
-                            l.cap);
-          n_sort = (long long)reserved;
-          pay = reinterpret_cast<const float*>(cpay);
-          if (n_sort == 0) {
-            VPS_HIP_CHECK(ctx, hipMemsetAsync(start, 0, sizeof(unsigned) * (l.nbricks + 1), ctx->stream));
-            return 1;     // (nothing to sort: start[] is all zero)
-          }
-          hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, StoredKeyOf<K>>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1,
-                             ctx->stream, StoredKeyOf<K>{keys}, n_sort, g, (K*)nullptr, table);
-        } else {
-          return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "slab-sized sort workspace: [rho v, rho] records only");
-        }
-      } else {
-        hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, DepKeyOf<F, K>>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1,
-                           ctx->stream, DepKeyOf<F, K>{pos, lcell, nsz, b}, (long long)np, g, keys, table);
-      }
+      const auto key = key_of(K{});
+      typedef typename std::remove_const<decltype(key)>::type Key;
+      // (keys that are already stored are not written again)
+      hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, Key>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
+                         key, n, g, std::is_same<Key, StoredKeyOf<K>>::value ? (K*)nullptr : keys, table);
       launch_exclusive_scan(ctx->stream, table, (long long)g.ngroups * g.nchunks, table_tiles, table_start);
       if (staged) {
-        const unsigned grid = (unsigned)(8 * ((g.nchunks + 7) / 8));
-        auto go = [&](auto src) -> int {      // src: where the payload comes from
-          auto kern = sort_scatter_staged_kernel<SORT_ITEMS, K, decltype(src)>;
-          if (lds_staged > 64 * 1024)
-            VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_staged));
-          hipLaunchKernelGGL(kern, dim3(grid), dim3(SORT_THREADS), lds_staged, ctx->stream, (const K*)keys, src, n_sort, g,
-                             table_start, rec1);
-          return VPS_OK;
-        };
-        int rcs;
-        if constexpr (C == 4) rcs = l.recompute ? go(DepPayload<4, false>{pay, rho}) : go(DepPayload<C, RHOV>{pay, rho});   // (compacted: [rho v, rho] as stored)
-        else rcs = go(DepPayload<C, RHOV>{pay, rho});
-        if (rcs) return rcs;
+        auto kern = sort_scatter_staged_kernel<SORT_ITEMS, K, Pay>;
+        if (int rcl = raise_lds_limit(ctx, kern, lds_staged)) return rcl;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((g.nchunks + 7) / 8))), dim3(SORT_THREADS), lds_staged, ctx->stream,
+                           (const K*)keys, pay, n, g, table_start, rec1);
       } else {
-        hipLaunchKernelGGL((sort_scatter_kernel<SORT_ITEMS, K, DepPayload<C, RHOV>>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS),
-                           lds1, ctx->stream, (const K*)keys, DepPayload<C, RHOV>{payload, rho}, (long long)np, g, table_start, rec1);
+        hipLaunchKernelGGL((sort_scatter_kernel<SORT_ITEMS, K, Pay>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
+                           (const K*)keys, pay, n, g, table_start, rec1);
       }
       return VPS_OK;
     };
     // (the keys[] region holds 8 bytes per particle either way: the atomic-rank path's keys are 64-bit)
     const int rc1 = l.wide_keys ? level1(reinterpret_cast<unsigned long long*>(work + l.keys))
                                 : level1(reinterpret_cast<unsigned*>(work + l.keys));
-    if (rc1 == 1) return VPS_OK;     // (empty slab)
     if (rc1) return rc1;
-    hipLaunchKernelGGL((sort_fine_kernel<C, true>), dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1,
-                       g, table_start, start, records);
+    hipLaunchKernelGGL((sort_fine_kernel<CR, true>), dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1, g,
+                       table_start, start, records);
   } else {
+    const auto key = key_of((unsigned long long)0);
+    typedef typename std::remove_const<decltype(key)>::type Key;
     unsigned* tiles = reinterpret_cast<unsigned*>(work + l.tiles);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(work + l.keys);
     unsigned* ranks = reinterpret_cast<unsigned*>(work + l.ranks);
     VPS_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(unsigned) * l.nbricks, ctx->stream));
-    const unsigned pblocks = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(brick_rank_kernel<F>, dim3(pblocks), dim3(256), 0, ctx->stream, pos, (long long)np, lcell,
-                       nsz, b, count, keys, ranks);
+    const unsigned pblocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(rank_kernel<Key>, dim3(pblocks), dim3(256), 0, ctx->stream, key, n, g.cells, count, keys, ranks);
     launch_exclusive_scan(ctx->stream, count, l.nbricks, tiles, start);
-    hipLaunchKernelGGL((brick_scatter_kernel<C, RHOV>), dim3(pblocks), dim3(256), 0, ctx->stream, keys, ranks,
-                       payload, rho, (long long)np, (unsigned)b.cells, start, records);
+    hipLaunchKernelGGL(rank_scatter_kernel<Pay>, dim3(pblocks), dim3(256), 0, ctx->stream, keys, ranks, pay, n, g.cells, start,
+                       records);
   }
   VPS_HIP_CHECK(ctx, hipGetLastError());
   return VPS_OK;
+}
+
+// The pre-stage of a slab-sized workspace (l.recompute): {key, [rho v, rho]} of the slab's particles, compact, into keys[] / cpay;
+// *n_sort: the slots handed out -- the slab's particles + at most one partly used block per workgroup.  One host synchronisation.
+template <typename F, int C, bool RHOV>
+int compact_slab(vps_ctx* ctx, const F* pos, const float* vel, const float* rho, int64_t np, F lcell, F nsz, const Bricks& b,
+                 const DepLayout& l, char* work, long long* n_sort) {
+  if (!(sort_staged() && sort_staged_lds(l.geom, C, SORT_ITEMS) <= ctx->lds_per_cu))
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "slab-sized sort workspace needs the LDS-staged scatter");
+  if constexpr (C == 4 && RHOV) {
+    unsigned long long* counter = reinterpret_cast<unsigned long long*>(work + l.counter);
+    float4* cpay = reinterpret_cast<float4*>(work + l.cpay);
+    VPS_HIP_CHECK(ctx, hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
+    const long long nch = (np + (long long)COMPACT_THREADS * COMPACT_ITEMS - 1) / ((long long)COMPACT_THREADS * COMPACT_ITEMS);
+    const unsigned cgrid = (unsigned)std::min<long long>(std::min<long long>(nch, (long long)ctx->num_cu * 8), COMPACT_MAXGRID);
+    auto launch = [&](auto* keys) {
+      typedef typename std::remove_pointer<decltype(keys)>::type K;
+      hipLaunchKernelGGL((slab_compact_kernel<F, K>), dim3(cgrid), dim3(COMPACT_THREADS), 0, ctx->stream, pos, vel, rho,
+                         (long long)np, lcell, nsz, b, l.geom, keys, cpay, counter, l.cap_in);
+    };
+    if (l.wide_keys) launch(reinterpret_cast<unsigned long long*>(work + l.keys));
+    else launch(reinterpret_cast<unsigned*>(work + l.keys));
+    unsigned long long reserved = 0;
+    VPS_HIP_CHECK(ctx, hipMemcpyAsync(&reserved, counter, sizeof(reserved), hipMemcpyDeviceToHost, ctx->stream));
+    VPS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((long long)reserved > l.cap_in)
+      return vps_fail(ctx, VPS_ERR_ARG, "more particles lie inside the slab than the workspace was sized for (%lld; vps_count_in_slab)",
+                      l.cap);
+    *n_sort = (long long)reserved;
+    return VPS_OK;
+  } else {
+    return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "slab-sized sort workspace: [rho v, rho] records only");
+  }
+}
+
+// particles -> records {cell-in-bucket, payload[C]} grouped by bucket + start[nbuckets + 1]
+template <typename F, int C, bool RHOV>
+int sort_into_buckets(vps_ctx* ctx, const F* pos, const float* payload, const float* rho, int64_t np, F lcell,
+                      F nsz, const Bricks& b, const DepLayout& l, char* work) {
+  vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
+  if constexpr (C == 4) {     // (dep_layout: no other record is compacted)
+    if (np > 0 && l.recompute) {
+      // filter first; the sort proper then sees the compacted arrays only: the stored keys, [rho v, rho] as stored
+      long long n_sort = 0;
+      if (int rc = compact_slab<F, C, RHOV>(ctx, pos, payload, rho, np, lcell, nsz, b, l, work, &n_sort)) return rc;
+      return sort_records(ctx, [&](auto k) { return StoredKeyOf<decltype(k)>{reinterpret_cast<const decltype(k)*>(work + l.keys)}; },
+                          DepPayload<4, false>{reinterpret_cast<const float*>(work + l.cpay), rho}, n_sort, l, work);
+    }
+  }
+  return sort_records(ctx, [&](auto k) { return DepKeyOf<F, decltype(k)>{pos, lcell, nsz, b}; }, DepPayload<C, RHOV>{payload, rho},
+                      (long long)np, l, work);
 }
 
 // The float each route's kernel receives for a quantity is decided here, one function per route, and nowhere else:
@@ -1035,16 +1095,10 @@ int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const flo
   if (rc) return rc;
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
-    long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    long long grid_wg = (long long)ctx->num_cu * per_cu;
-    if (grid_wg > l.nbricks) grid_wg = l.nbricks;
     auto launch = [&](auto q) -> int {
       auto kern = brick_accumulate_kernel<C, EPI, decltype(q)::value>;
-      if (lds > 64 * 1024)
-        VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+      if (int rcl = raise_lds_limit(ctx, kern, lds)) return rcl;
+      hipLaunchKernelGGL(kern, dim3(brick_launch_grid(ctx, lds, l.nbricks)), dim3(256), lds, ctx->stream,
                          records, start, b, l.nbricks, flags, brick_par(ctx, decltype(q)::value, vol), grid);
       return VPS_OK;
     };
@@ -1110,11 +1164,29 @@ __device__ __forceinline__ double assign_base_cell(double s) {
   return ORDER == 2 ? floor(s - 0.5) : floor(s) - 1.0;
 }
 
-template <typename F, typename K, int ORDER>
+// The slab window of the fused form (vps_deposit_field with VPS_FLAG_ASSIGN): one more way of being invalid, a particle none of
+// whose ORDER target rows (c0x + j) mod N lies in [x0, x0 + nx).  Those rows are in the slab exactly when c0x lies in the window
+// [x0 - (ORDER - 1), x0 + nx - 1] mod N, i.e. (c0x - xlo) mod N < span with xlo = x0 - (ORDER - 1), span = nx + ORDER - 1; with
+// span >= N every particle passes.  The whole grid has no window: nothing of the test exists in its key.
+struct WholeGrid {
+  __device__ __forceinline__ bool keeps(int, int) const { return true; }
+};
+struct SlabWindow {
+  int xlo, span;
+  __device__ __forceinline__ bool keeps(int c0x, int N) const {
+    int d = c0x - xlo;                               // in (-N, N + ORDER - 1)
+    if (d < 0) d += N;
+    if (d >= N) d -= N;
+    return d < span;
+  }
+};
+
+template <typename F, typename K, int ORDER, typename Window>
 struct AssignKeyOf {
   const F* __restrict__ pos;
   double lcell, n;
-  Bricks b;
+  Bricks b;       // make_bricks(N, 0, N, C): the whole grid's, whatever the window
+  Window window;
   __device__ __forceinline__ K operator()(long long i) const {
     int c[3];
 #pragma unroll
@@ -1123,6 +1195,7 @@ struct AssignKeyOf {
       const double r = f0 - floor(f0 / n) * n;          // wrap_cell, before its conversion
       if (!(r >= 0.0 && r < n)) return sort_invalid<K>();   // NaN, inf, beyond 2^53
       c[a] = (int)r;
+      if (a == 0 && !window.keeps(c[0], b.N)) return sort_invalid<K>();         // no target row in the slab
     }
     const int ix = c[0] / b.bx, iy = c[1] / b.by, iz = c[2] / b.bz;
     const unsigned brick = (unsigned)((ix * b.nby + iy) * b.nbz + iz);
@@ -1131,90 +1204,38 @@ struct AssignKeyOf {
   }
 };
 
-// payload[C] and, per axis, TWO float32 numbers each rounded once from float64, so that a small weight keeps its relative
-// precision (a weight of 1e-9 next to a cell centre would lose all of it if 1 - f were formed in float32 from a rounded f):
+// Per axis TWO float32 numbers each rounded once from float64, so that a small weight keeps its relative precision (a weight of
+// 1e-9 next to a cell centre would lose all of it if 1 - f were formed in float32 from a rounded f):
 //   CIC: (float)(1 - f), (float)f                         -- the two weights themselves
 //   TSC: a = (float)(1/2 - d), b = (float)(1/2 + d)       -- weights a a / 2, 1/2 + a b (= 3/4 - d^2), b b / 2 (assign_axis_weights)
-template <typename F, int CP, int ORDER>
+template <int ORDER, typename F>
+__device__ __forceinline__ void assign_weight_words(const F* __restrict__ pos, long long i, double lcell, float out6[6]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double s = (double)pos[i * 3 + a] / lcell;
+    if constexpr (ORDER == 2) {
+      const double f = s - 0.5 - floor(s - 0.5);
+      out6[2 * a] = (float)(1.0 - f);
+      out6[2 * a + 1] = (float)f;
+    } else {
+      const double d = s - (floor(s) + 0.5);
+      out6[2 * a] = (float)(0.5 - d);
+      out6[2 * a + 1] = (float)(0.5 + d);
+    }
+  }
+}
+
+// payload[CP] (RHOV: [rho v, rho] built on the fly from `payload` = vel and rho, load_payload) and the six weight words
+template <typename F, int CP, bool RHOV, int ORDER>
 struct AssignPayload {
   static constexpr int C = CP + 6;
   const F* __restrict__ pos;
   const float* __restrict__ payload;
-  double lcell;
-  __device__ __forceinline__ void load(long long i, float val[CP + 6]) const {
-    load_payload<CP, false>(payload, nullptr, i, val);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double s = (double)pos[i * 3 + a] / lcell;
-      if constexpr (ORDER == 2) {
-        const double f = s - 0.5 - floor(s - 0.5);
-        val[CP + 2 * a] = (float)(1.0 - f);
-        val[CP + 2 * a + 1] = (float)f;
-      } else {
-        const double d = s - (floor(s) + 0.5);
-        val[CP + 2 * a] = (float)(0.5 - d);
-        val[CP + 2 * a + 1] = (float)(0.5 + d);
-      }
-    }
-  }
-};
-
-// ---- the fused form on an x-slab (vps_deposit_field with VPS_FLAG_ASSIGN) --------------------------------------------------
-// The key of AssignKeyOf -- the bricks of the WHOLE grid -- with one more way of being invalid: a particle none of whose ORDER
-// target rows (c0x + j) mod N lies in [x0, x0 + nx).  Those rows are in the slab exactly when c0x lies in the window
-// [x0 - (ORDER - 1), x0 + nx - 1] mod N, i.e. (c0x - xlo) mod N < span with xlo = x0 - (ORDER - 1), span = nx + ORDER - 1; with
-// span >= N every particle passes.  The expressions of AssignKeyOf, restated (not shared: its kernels stay what they are).
-template <typename F, typename K, int ORDER>
-struct AssignSlabKeyOf {
-  const F* __restrict__ pos;
-  double lcell, n;
-  Bricks b;       // make_bricks(N, 0, N, 4): the whole grid's
-  int xlo, span;
-  __device__ __forceinline__ K operator()(long long i) const {
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double f0 = assign_base_cell<ORDER>((double)pos[i * 3 + a] / lcell);
-      const double r = f0 - floor(f0 / n) * n;          // wrap_cell, before its conversion
-      if (!(r >= 0.0 && r < n)) return sort_invalid<K>();   // NaN, inf, beyond 2^53
-      c[a] = (int)r;
-      if (a == 0) {
-        int d = c[0] - xlo;                              // in (-N, N + ORDER - 1)
-        if (d < 0) d += b.N;
-        if (d >= b.N) d -= b.N;
-        if (d >= span) return sort_invalid<K>();         // no target row in the slab
-      }
-    }
-    const int ix = c[0] / b.bx, iy = c[1] / b.by, iz = c[2] / b.bz;
-    const unsigned brick = (unsigned)((ix * b.nby + iy) * b.nbz + iz);
-    const unsigned loc = (unsigned)(((c[0] - ix * b.bx) * b.by + (c[1] - iy * b.by)) * b.bz + (c[2] - iz * b.bz));
-    return (K)brick * (unsigned)b.cells + loc;
-  }
-};
-
-// AssignPayload with the [rho v, rho] payload built on the fly (the RHOV form of load_payload), the six weight words as there
-template <typename F, int ORDER>
-struct AssignRhovPayload {
-  static constexpr int C = 4 + 6;
-  const F* __restrict__ pos;
-  const float* __restrict__ vel;
   const float* __restrict__ rho;
   double lcell;
-  __device__ __forceinline__ void load(long long i, float val[4 + 6]) const {
-    load_payload<4, true>(vel, rho, i, val);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double s = (double)pos[i * 3 + a] / lcell;
-      if constexpr (ORDER == 2) {
-        const double f = s - 0.5 - floor(s - 0.5);
-        val[4 + 2 * a] = (float)(1.0 - f);
-        val[4 + 2 * a + 1] = (float)f;
-      } else {
-        const double d = s - (floor(s) + 0.5);
-        val[4 + 2 * a] = (float)(0.5 - d);
-        val[4 + 2 * a + 1] = (float)(0.5 + d);
-      }
-    }
+  __device__ __forceinline__ void load(long long i, float val[CP + 6]) const {
+    load_payload<CP, RHOV>(payload, rho, i, val);
+    assign_weight_words<ORDER>(pos, i, lcell, val + CP);
   }
 };
 
@@ -1248,42 +1269,85 @@ __host__ __device__ inline int assign_axis_sources(int i, int bw, int N, int ord
   return n;
 }
 
-// one-atomic-per-particle ranking with the key of any functor (option sort_atomic, or a geometry the two-level sort does not
-// cover): what brick_rank_kernel / brick_scatter_kernel do for the NGP key and payload
-template <typename KeyOf>
-__global__ void __launch_bounds__(256)
-    assign_rank_kernel(KeyOf key_of, long long np, unsigned cells, unsigned* __restrict__ count,
-                       unsigned long long* __restrict__ keys, unsigned* __restrict__ ranks) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  const unsigned long long key = key_of(i);
-  keys[i] = key;
-  if (key != ~0ull) ranks[i] = atomicAdd(&count[key / cells], 1u);
-}
-
-template <typename Payload>
-__global__ void __launch_bounds__(256)
-    assign_scatter_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ ranks, Payload pay,
-                          long long np, unsigned cells, const unsigned* __restrict__ start, unsigned* __restrict__ records) {
-  constexpr int C = Payload::C;
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  const unsigned long long key = keys[i];
-  if (key == ~0ull) return;
-  float val[C];
-  pay.load(i, val);
-  unsigned* rec = records + (size_t)(start[key / cells] + ranks[i]) * (C + 1);
-  rec[0] = (unsigned)(key % cells);
+// The owner-computes gather of brick (ix, iy, iz): records {cell-in-brick of c0, payload[C], 6 weight words} of its source buckets
+// -> LDS float adds into tile [CT][cells].  The brick owns the cells of its range (the last brick of an axis may be partial) on
+// the x rows [cx0, cx1): the whole range, or its part inside a slab -- the other rows of the tile are never added to.  CT = C + 1:
+// the second-moment channel, rho_p |v_p|^2 of [rho v, rho] records, behind the C record channels (TileOut).
+// (`b` by reference: by value the kernels lose 1 - 2 % of their instructions and take up to 4 more VGPRs; DESIGN.md has both)
+template <int C, int CT, int ORDER>
+__device__ __forceinline__ void assign_gather(const unsigned* __restrict__ records, const unsigned* __restrict__ start,
+                                              const Bricks& b, int ix, int iy, int iz, int cx0, int cx1, float* tile) {
+  constexpr int W = C + 7;
+  const int cells = b.cells, N = b.N;
+  const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
+  const int gy1 = min(gy0 + b.by, N), gz1 = min(gz0 + b.bz, N);
+  int srcx[3], srcy[3], srcz[3];
+  const int nsx = assign_axis_sources(ix, b.bx, N, ORDER, srcx);
+  const int nsy = assign_axis_sources(iy, b.by, N, ORDER, srcy);
+  const int nsz = assign_axis_sources(iz, b.bz, N, ORDER, srcz);
+  for (int sx = 0; sx < nsx; ++sx)
+    for (int sy = 0; sy < nsy; ++sy)
+      for (int sz = 0; sz < nsz; ++sz) {
+        const long long sb = ((long long)srcx[sx] * b.nby + srcy[sy]) * b.nbz + srcz[sz];
+        const unsigned s = start[sb], e = start[sb + 1];
+        const int ox = srcx[sx] * b.bx, oy = srcy[sy] * b.by, oz = srcz[sz] * b.bz;     // first cell of the source brick
+        for (unsigned j = s + threadIdx.x; j < e; j += blockDim.x) {
+          const unsigned* rec = records + (size_t)j * W;
+          int lz, ly, lx;
+          brick_cell(b, (int)rec[0], lx, ly, lz);
+          // target cells per axis, relative to this brick; a record none of whose targets on some axis is ours is dropped
+          // before its payload and weights are read (most records of a neighbour's bucket)
+          int tx[ORDER], ty[ORDER], tz[ORDER];
+          bool anyx = false, anyy = false, anyz = false;
 #pragma unroll
-  for (int c = 0; c < C; ++c) rec[1 + c] = __float_as_uint(val[c]);
+          for (int k = 0; k < ORDER; ++k) {
+            int t = ox + lx + k;
+            if (t >= N) t %= N;
+            tx[k] = (t >= cx0 && t < cx1) ? t - gx0 : -1;
+            anyx = anyx || tx[k] >= 0;
+            t = oy + ly + k;
+            if (t >= N) t %= N;
+            ty[k] = (t >= gy0 && t < gy1) ? t - gy0 : -1;
+            anyy = anyy || ty[k] >= 0;
+            t = oz + lz + k;
+            if (t >= N) t %= N;
+            tz[k] = (t >= gz0 && t < gz1) ? t - gz0 : -1;
+            anyz = anyz || tz[k] >= 0;
+          }
+          if (!(anyx && anyy && anyz)) continue;
+          float pay[CT], wx[ORDER], wy[ORDER], wz[ORDER];
+#pragma unroll
+          for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
+          // (the particle's rho_p |v_p|^2, once per record: it takes the same weight product as the four channels)
+          if constexpr (CT > C) pay[C] = second_moment_term(pay[0], pay[1], pay[2], pay[3]);
+          assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
+          assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
+          assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
+#pragma unroll
+          for (int kx = 0; kx < ORDER; ++kx) {
+            if (tx[kx] < 0) continue;
+#pragma unroll
+            for (int ky = 0; ky < ORDER; ++ky) {
+              if (ty[ky] < 0) continue;
+#pragma unroll
+              for (int kz = 0; kz < ORDER; ++kz) {
+                if (tz[kz] < 0) continue;
+                const float wt = wx[kx] * wy[ky] * wz[kz];      // (the product order of assign_expand_kernel)
+                const int at = (tx[kx] * b.by + ty[ky]) * b.bz + tz[kz];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
+              }
+            }
+          }
+        }
+      }
 }
 
-// records {cell-in-brick of c0, payload[C], 6 weight words} grouped by the brick of c0 -> grid [C][N][N][N], every cell written
+// records grouped by the brick of c0 -> grid [C][N][N][N] of raw channels, every cell written
 template <int C, int ORDER>
 __global__ void __launch_bounds__(256)
     assign_accumulate_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start, Bricks b,
                              long long nbricks, float* __restrict__ grid) {
-  constexpr int W = C + 7;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* tile = reinterpret_cast<float*>(smem_raw);  // [C][cells]
   const int cells = b.cells, N = b.N;
@@ -1292,116 +1356,30 @@ __global__ void __launch_bounds__(256)
   const long long plane = (long long)N * N * N;
   __syncthreads();
   for (long long brick = blockIdx.x; brick < nbricks; brick += gridDim.x) {
-    const int iz = (int)(brick % b.nbz), iy = (int)((brick / b.nbz) % b.nby);
-    const int ix = (int)(brick / ((long long)b.nbz * b.nby));
+    int ix, iy, iz;
+    brick_index(b, brick, ix, iy, iz);
     const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
-    // the cells this brick owns: [g0, g1) per axis (the last brick of an axis may be partial)
-    const int gx1 = min(gx0 + b.bx, N), gy1 = min(gy0 + b.by, N), gz1 = min(gz0 + b.bz, N);
-    int srcx[3], srcy[3], srcz[3];
-    const int nsx = assign_axis_sources(ix, b.bx, N, ORDER, srcx);
-    const int nsy = assign_axis_sources(iy, b.by, N, ORDER, srcy);
-    const int nsz = assign_axis_sources(iz, b.bz, N, ORDER, srcz);
-    for (int sx = 0; sx < nsx; ++sx)
-      for (int sy = 0; sy < nsy; ++sy)
-        for (int sz = 0; sz < nsz; ++sz) {
-          const long long sb = ((long long)srcx[sx] * b.nby + srcy[sy]) * b.nbz + srcz[sz];
-          const unsigned s = start[sb], e = start[sb + 1];
-          const int ox = srcx[sx] * b.bx, oy = srcy[sy] * b.by, oz = srcz[sz] * b.bz;     // first cell of the source brick
-          for (unsigned j = s + threadIdx.x; j < e; j += blockDim.x) {
-            const unsigned* rec = records + (size_t)j * W;
-            const int loc = (int)rec[0];
-            int lz, ly, lx;
-            if (b.pow2) {
-              lz = loc & (b.bz - 1);
-              ly = (loc >> b.sz) & (b.by - 1);
-              lx = loc >> (b.sz + b.sy);
-            } else {
-              lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
-            }
-            // target cells per axis, relative to this brick; a record none of whose targets on some axis is ours is dropped
-            // before its payload and weights are read (most records of a neighbour's bucket)
-            int tx[ORDER], ty[ORDER], tz[ORDER];
-            bool anyx = false, anyy = false, anyz = false;
-#pragma unroll
-            for (int k = 0; k < ORDER; ++k) {
-              int t = ox + lx + k;
-              if (t >= N) t %= N;
-              tx[k] = (t >= gx0 && t < gx1) ? t - gx0 : -1;
-              anyx = anyx || tx[k] >= 0;
-              t = oy + ly + k;
-              if (t >= N) t %= N;
-              ty[k] = (t >= gy0 && t < gy1) ? t - gy0 : -1;
-              anyy = anyy || ty[k] >= 0;
-              t = oz + lz + k;
-              if (t >= N) t %= N;
-              tz[k] = (t >= gz0 && t < gz1) ? t - gz0 : -1;
-              anyz = anyz || tz[k] >= 0;
-            }
-            if (!(anyx && anyy && anyz)) continue;
-            float pay[C], wx[ORDER], wy[ORDER], wz[ORDER];
-#pragma unroll
-            for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
-            assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
-            assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
-            assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
-#pragma unroll
-            for (int kx = 0; kx < ORDER; ++kx) {
-              if (tx[kx] < 0) continue;
-#pragma unroll
-              for (int ky = 0; ky < ORDER; ++ky) {
-                if (ty[ky] < 0) continue;
-#pragma unroll
-                for (int kz = 0; kz < ORDER; ++kz) {
-                  if (tz[kz] < 0) continue;
-                  const float wt = wx[kx] * wy[ky] * wz[kz];      // (the product order of assign_expand_kernel)
-                  const int at = (tx[kx] * b.by + ty[ky]) * b.bz + tz[kz];
-#pragma unroll
-                  for (int c = 0; c < C; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
-                }
-              }
-            }
-          }
-        }
+    assign_gather<C, C, ORDER>(records, start, b, ix, iy, iz, gx0, min(gx0 + b.bx, N), tile);
     __syncthreads();
     // stream the tile out (rows of bz cells are contiguous in the grid) and zero it for the next brick
     if (vec4) {
-      typedef float vf4 __attribute__((ext_vector_type(4)));
       for (int i = threadIdx.x; i < cells / 4; i += blockDim.x) {
         const int loc = i * 4;
         int lz, ly, lx;
-        if (b.pow2) {
-          lz = loc & (b.bz - 1);
-          ly = (loc >> b.sz) & (b.by - 1);
-          lx = loc >> (b.sz + b.sy);
-        } else {
-          lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
-        }
+        brick_cell(b, loc, lx, ly, lz);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
         const bool inside = gx < N && gy < N && gz < N;      // (N and bz multiples of 4: a quad is inside or outside as a whole)
         const long long cell = ((long long)gx * N + gy) * N + gz;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          float4* t = reinterpret_cast<float4*>(tile + c * cells + loc);
-          const float4 val = *t;
-          *t = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (inside) {
-            vf4 q; q.x = val.x; q.y = val.y; q.z = val.z; q.w = val.w;
-            __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(grid + c * plane + cell));
-          }
-        }
+        tile_out4<C, EPI_RAW, VPS_VELOCITY, true>(tile, cells, loc, inside, 0, CellPar{}, grid, plane, cell);
       }
     } else {
       for (int loc = threadIdx.x; loc < cells; loc += blockDim.x) {
-        const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
+        int lz, ly, lx;
+        brick_cell<false>(b, loc, lx, ly, lz);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
         const bool inside = gx < N && gy < N && gz < N;
         const long long cell = ((long long)gx * N + gy) * N + gz;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          const float v = tile[c * cells + loc];
-          tile[c * cells + loc] = 0.f;
-          if (inside) __builtin_nontemporal_store(v, grid + c * plane + cell);
-        }
+        tile_out1<C, EPI_RAW, VPS_VELOCITY, true>(tile, cells, loc, inside, 0, CellPar{}, grid, plane, cell);
       }
     }
     __syncthreads();   // tile is all zero again
@@ -1410,22 +1388,17 @@ __global__ void __launch_bounds__(256)
 
 // The fused form of the direct route on an x-slab: records {cell-in-brick of c0, [rho v, rho], 6 weight words} grouped by the
 // brick of c0 in the WHOLE grid's geometry `b` (x0 = 0, nx = N) -> the fields of QUANT on the rows [x0, x0 + nx), out
-// [NOUT][nx][N][N], every cell written exactly once.  The gather loop and its LDS float adds are assign_accumulate_kernel's with
-// C = 4, the epilogue is brick_accumulate_kernel<4, EPI_ALGEBRA, QUANT>'s (`par`: brick_par).  Three things differ from the whole
-// grid: only the bricks [first, first + nbricks) whose x range meets the slab are walked; a brick owns its cells on the rows
-// [cx0, cx1) = its x range clipped to the slab only (the other rows of its tile are never added to and never read); and the
-// stream-out addresses row gx - x0 with plane stride nx N N.
+// [NOUT][nx][N][N], every cell written exactly once; `par`: brick_par.  Three things differ from the whole grid: only the bricks
+// [first, first + nbricks) whose x range meets the slab are walked; a brick owns its cells on the rows [cx0, cx1) = its x range
+// clipped to the slab only (the other rows of its tile are never added to and never read); and the stream-out addresses row
+// gx - x0 with plane stride nx N N.
 template <int ORDER, int QUANT>
 __global__ void __launch_bounds__(256)
     assign_field_kernel(const unsigned* __restrict__ records, const unsigned* __restrict__ start, Bricks b, long long first,
                         long long nbricks, int x0, int nx, int flags, float par, float* __restrict__ out) {
-  constexpr int C = 4, W = C + 7;
-  constexpr int NOUT = vps_quantity_channels(QUANT);
-  const int cflags = (vps_quantity_needs_alpha(QUANT) || vps_quantity_scalar_rho(QUANT)) ? 0 : flags;
+  constexpr int C = 4, CT = TileOut<C, EPI_ALGEBRA, QUANT>::CT;
+  const int cflags = tile_cflags<QUANT>(flags);
   const CellPar cpar{par, par};     // (one float, copied into both members: brick_accumulate_kernel)
-  // (compile time, as there: the second-moment quantities keep S2 = sum w rho_p |v_p|^2 in a fifth tile channel)
-  constexpr bool M2 = vps_quantity_second_moment(QUANT);
-  constexpr int CT = M2 ? C + 1 : C;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* tile = reinterpret_cast<float*>(smem_raw);  // [CT][cells]
   const int cells = b.cells, N = b.N;
@@ -1435,137 +1408,31 @@ __global__ void __launch_bounds__(256)
   const int rowcells = b.by * b.bz;       // cells of one x row of the tile
   __syncthreads();
   for (long long t = blockIdx.x; t < nbricks; t += gridDim.x) {
-    const long long brick = first + t;
-    const int iz = (int)(brick % b.nbz), iy = (int)((brick / b.nbz) % b.nby);
-    const int ix = (int)(brick / ((long long)b.nbz * b.nby));
+    int ix, iy, iz;
+    brick_index(b, first + t, ix, iy, iz);
     const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
-    // the cells this brick owns: its range (the last brick of an axis may be partial), on x clipped to the slab
-    const int gy1 = min(gy0 + b.by, N), gz1 = min(gz0 + b.bz, N);
     const int cx0 = max(gx0, x0), cx1 = min(min(gx0 + b.bx, N), x0 + nx);
-    int srcx[3], srcy[3], srcz[3];
-    const int nsx = assign_axis_sources(ix, b.bx, N, ORDER, srcx);
-    const int nsy = assign_axis_sources(iy, b.by, N, ORDER, srcy);
-    const int nsz = assign_axis_sources(iz, b.bz, N, ORDER, srcz);
-    for (int sx = 0; sx < nsx; ++sx)
-      for (int sy = 0; sy < nsy; ++sy)
-        for (int sz = 0; sz < nsz; ++sz) {
-          const long long sb = ((long long)srcx[sx] * b.nby + srcy[sy]) * b.nbz + srcz[sz];
-          const unsigned s = start[sb], e = start[sb + 1];
-          const int ox = srcx[sx] * b.bx, oy = srcy[sy] * b.by, oz = srcz[sz] * b.bz;     // first cell of the source brick
-          for (unsigned j = s + threadIdx.x; j < e; j += blockDim.x) {
-            const unsigned* rec = records + (size_t)j * W;
-            const int loc = (int)rec[0];
-            int lz, ly, lx;
-            if (b.pow2) {
-              lz = loc & (b.bz - 1);
-              ly = (loc >> b.sz) & (b.by - 1);
-              lx = loc >> (b.sz + b.sy);
-            } else {
-              lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
-            }
-            int tx[ORDER], ty[ORDER], tz[ORDER];
-            bool anyx = false, anyy = false, anyz = false;
-#pragma unroll
-            for (int k = 0; k < ORDER; ++k) {
-              int q = ox + lx + k;
-              if (q >= N) q %= N;
-              tx[k] = (q >= cx0 && q < cx1) ? q - gx0 : -1;
-              anyx = anyx || tx[k] >= 0;
-              q = oy + ly + k;
-              if (q >= N) q %= N;
-              ty[k] = (q >= gy0 && q < gy1) ? q - gy0 : -1;
-              anyy = anyy || ty[k] >= 0;
-              q = oz + lz + k;
-              if (q >= N) q %= N;
-              tz[k] = (q >= gz0 && q < gz1) ? q - gz0 : -1;
-              anyz = anyz || tz[k] >= 0;
-            }
-            if (!(anyx && anyy && anyz)) continue;
-            float pay[CT], wx[ORDER], wy[ORDER], wz[ORDER];
-#pragma unroll
-            for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
-            // (the particle's rho_p |v_p|^2, once per record: it takes the same weight product as the four channels)
-            if constexpr (M2) pay[C] = second_moment_term(pay[0], pay[1], pay[2], pay[3]);
-            assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
-            assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
-            assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
-#pragma unroll
-            for (int kx = 0; kx < ORDER; ++kx) {
-              if (tx[kx] < 0) continue;
-#pragma unroll
-              for (int ky = 0; ky < ORDER; ++ky) {
-                if (ty[ky] < 0) continue;
-#pragma unroll
-                for (int kz = 0; kz < ORDER; ++kz) {
-                  if (tz[kz] < 0) continue;
-                  const float wt = wx[kx] * wy[ky] * wz[kz];      // (the product order of assign_expand_kernel)
-                  const int at = (tx[kx] * b.by + ty[ky]) * b.bz + tz[kz];
-#pragma unroll
-                  for (int c = 0; c < CT; ++c) atomicAdd(&tile[c * cells + at], pay[c] * wt);
-                }
-              }
-            }
-          }
-        }
+    assign_gather<C, CT, ORDER>(records, start, b, ix, iy, iz, cx0, cx1, tile);
     __syncthreads();
     // stream the owned rows out (rows of bz cells are contiguous in the slab) and zero them for the next brick
     const int loc_lo = (cx0 - gx0) * rowcells, loc_hi = (cx1 - gx0) * rowcells;
     if (vec4) {
-      typedef float vf4 __attribute__((ext_vector_type(4)));
-      const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int loc = loc_lo + 4 * (int)threadIdx.x; loc < loc_hi; loc += 4 * (int)blockDim.x) {
         int lz, ly, lx;
-        if (b.pow2) {
-          lz = loc & (b.bz - 1);
-          ly = (loc >> b.sz) & (b.by - 1);
-          lx = loc >> (b.sz + b.sy);
-        } else {
-          lz = loc % b.bz; ly = (loc / b.bz) % b.by; lx = loc / (b.bz * b.by);
-        }
+        brick_cell(b, loc, lx, ly, lz);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
         const bool inside = gy < N && gz < N;      // (gx is inside by the loop's bounds; N and bz multiples of 4: whole quads)
         const long long cell = ((long long)(gx - x0) * N + gy) * N + gz;
-        float4* t0 = reinterpret_cast<float4*>(tile + loc);
-        float4* t1 = reinterpret_cast<float4*>(tile + cells + loc);
-        float4* t2 = reinterpret_cast<float4*>(tile + 2 * cells + loc);
-        float4* t3 = reinterpret_cast<float4*>(tile + 3 * cells + loc);
-        const float4 c0 = *t0, c1 = *t1, c2 = *t2, c3 = *t3;
-        *t0 = zero4; *t1 = zero4; *t2 = zero4; *t3 = zero4;
-        float4 c4 = zero4;                       // the second moment (M2 only: a constant elsewhere)
-        if constexpr (M2) {
-          float4* t4 = reinterpret_cast<float4*>(tile + 4 * cells + loc);
-          c4 = *t4;
-          *t4 = zero4;
-        }
-        if (inside) {
-          float rx[4], ry[4], rz[4], rw[4];
-          cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
-          cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
-          cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
-          cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
-#pragma unroll
-          for (int c = 0; c < NOUT; ++c) {
-            vf4 q; q.x = rx[c]; q.y = ry[c]; q.z = rz[c]; q.w = rw[c];
-            __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(out + c * plane + cell));
-          }
-        }
+        tile_out4<C, EPI_ALGEBRA, QUANT, true>(tile, cells, loc, inside, cflags, cpar, out, plane, cell);
       }
     } else {
       for (int loc = loc_lo + (int)threadIdx.x; loc < loc_hi; loc += (int)blockDim.x) {
-        const int lz = loc % b.bz, ly = (loc / b.bz) % b.by, lx = loc / (b.bz * b.by);
+        int lz, ly, lx;
+        brick_cell<false>(b, loc, lx, ly, lz);
         const int gx = gx0 + lx, gy = gy0 + ly, gz = gz0 + lz;
-        float v[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          v[c] = tile[c * cells + loc];
-          tile[c * cells + loc] = 0.f;
-        }
-        if (gy >= N || gz >= N) continue;
+        const bool inside = gy < N && gz < N;
         const long long cell = ((long long)(gx - x0) * N + gy) * N + gz;
-        float r[4];
-        cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, v[CT - 1]);
-#pragma unroll
-        for (int c = 0; c < NOUT; ++c) __builtin_nontemporal_store(r[c], out + c * plane + cell);
+        tile_out1<C, EPI_ALGEBRA, QUANT, true>(tile, cells, loc, inside, cflags, cpar, out, plane, cell);
       }
     }
     __syncthreads();   // the owned rows are all zero again (the others were never touched)
@@ -1594,74 +1461,6 @@ int check_assign_args(vps_ctx* ctx, const char* who, int64_t np, int C, int N, i
   return VPS_OK;
 }
 
-// particles -> records grouped by the brick of c0 + start[]: sort_into_buckets with the key and payload of the direct route.
-// pay: the payload functor (AssignPayload, AssignRhovPayload); key_of(K{}): the key functor for keys of type K (AssignKeyOf,
-// AssignSlabKeyOf).
-template <typename Pay, typename KeyMaker>
-int assign_sort(vps_ctx* ctx, const Pay& pay, KeyMaker key_of, int64_t np, const AssignPlan& p, char* work) {
-  constexpr int CR = Pay::C;
-  const Bricks& b = p.b;
-  const DepLayout& l = p.l;
-  unsigned* count = reinterpret_cast<unsigned*>(work + l.count);
-  unsigned* start = reinterpret_cast<unsigned*>(work + l.start);
-  unsigned* records = reinterpret_cast<unsigned*>(work + l.records);
-  vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
-  if (np == 0) {
-    VPS_HIP_CHECK(ctx, hipMemsetAsync(start, 0, sizeof(unsigned) * (l.nbricks + 1), ctx->stream));
-    return VPS_OK;
-  }
-  if (l.two_level) {
-    const SortGeom& g = l.geom;
-    unsigned* table = reinterpret_cast<unsigned*>(work + l.table);
-    unsigned* table_start = reinterpret_cast<unsigned*>(work + l.table_start);
-    unsigned* table_tiles = reinterpret_cast<unsigned*>(work + l.table_tiles);
-    unsigned* rec1 = reinterpret_cast<unsigned*>(work + l.rec1);
-    const size_t lds1 = sort_hist_lds(g), lds2 = sort_fine_lds(g);
-    const size_t lds_staged = sort_staged_lds(g, CR, SORT_ITEMS);
-    const bool staged = sort_staged() && lds_staged <= ctx->lds_per_cu;
-    auto level1 = [&](auto* keys) -> int {
-      typedef typename std::remove_pointer<decltype(keys)>::type K;
-      const auto key = key_of(K{});
-      typedef typename std::remove_const<decltype(key)>::type Key;
-      hipLaunchKernelGGL((sort_hist_kernel<SORT_ITEMS, K, Key>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
-                         key, (long long)np, g, keys, table);
-      launch_exclusive_scan(ctx->stream, table, (long long)g.ngroups * g.nchunks, table_tiles, table_start);
-      if (staged) {
-        auto kern = sort_scatter_staged_kernel<SORT_ITEMS, K, Pay>;
-        if (lds_staged > 64 * 1024)
-          VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds_staged));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((g.nchunks + 7) / 8))), dim3(SORT_THREADS), lds_staged, ctx->stream,
-                           (const K*)keys, pay, (long long)np, g, table_start, rec1);
-      } else {
-        hipLaunchKernelGGL((sort_scatter_kernel<SORT_ITEMS, K, Pay>), dim3((unsigned)g.nchunks), dim3(SORT_THREADS), lds1, ctx->stream,
-                           (const K*)keys, pay, (long long)np, g, table_start, rec1);
-      }
-      return VPS_OK;
-    };
-    const int rc1 = l.wide_keys ? level1(reinterpret_cast<unsigned long long*>(work + l.keys))
-                                : level1(reinterpret_cast<unsigned*>(work + l.keys));
-    if (rc1) return rc1;
-    hipLaunchKernelGGL((sort_fine_kernel<CR, true>), dim3((unsigned)g.ngroups), dim3(FINE_THREADS), lds2, ctx->stream, rec1, g,
-                       table_start, start, records);
-  } else {
-    const auto key = key_of((unsigned long long)0);
-    typedef typename std::remove_const<decltype(key)>::type Key;
-    unsigned* tiles = reinterpret_cast<unsigned*>(work + l.tiles);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(work + l.keys);
-    unsigned* ranks = reinterpret_cast<unsigned*>(work + l.ranks);
-    VPS_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(unsigned) * l.nbricks, ctx->stream));
-    const unsigned pblocks = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(assign_rank_kernel<Key>, dim3(pblocks), dim3(256), 0, ctx->stream, key, (long long)np, (unsigned)b.cells,
-                       count, keys, ranks);
-    launch_exclusive_scan(ctx->stream, count, l.nbricks, tiles, start);
-    hipLaunchKernelGGL(assign_scatter_kernel<Pay>, dim3(pblocks), dim3(256), 0, ctx->stream, keys, ranks, pay, (long long)np,
-                       (unsigned)b.cells, start, records);
-  }
-  VPS_HIP_CHECK(ctx, hipGetLastError());
-  return VPS_OK;
-}
-
 template <typename F, int C, int ORDER>
 int deposit_assign_run(vps_ctx* ctx, const void* pos_v, const float* payload, int64_t np, int N, double Lbox, float* grid,
                        void* work_v) {
@@ -1669,18 +1468,16 @@ int deposit_assign_run(vps_ctx* ctx, const void* pos_v, const float* payload, in
   char* work = reinterpret_cast<char*>(work_v);
   const double lcell = Lbox / (double)N;      // float64 whatever the dtype of pos (assign_expand_kernel's)
   const F* pos = reinterpret_cast<const F*>(pos_v);
-  const int rc = assign_sort(ctx, AssignPayload<F, C, ORDER>{pos, payload, lcell},
-                             [&](auto k) { return AssignKeyOf<F, decltype(k), ORDER>{pos, lcell, (double)N, p.b}; }, np, p, work);
-  if (rc) return rc;
+  {
+    vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
+    const int rc = sort_records(ctx, [&](auto k) { return AssignKeyOf<F, decltype(k), ORDER, WholeGrid>{pos, lcell, (double)N, p.b, {}}; },
+                                AssignPayload<F, C, false, ORDER>{pos, payload, nullptr, lcell}, (long long)np, p.l, work);
+    if (rc) return rc;
+  }
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
     const size_t lds = (size_t)C * p.b.cells * sizeof(float);
-    long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    long long grid_wg = (long long)ctx->num_cu * per_cu;
-    if (grid_wg > p.l.nbricks) grid_wg = p.l.nbricks;
-    hipLaunchKernelGGL((assign_accumulate_kernel<C, ORDER>), dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+    hipLaunchKernelGGL((assign_accumulate_kernel<C, ORDER>), dim3(brick_launch_grid(ctx, lds, p.l.nbricks)), dim3(256), lds, ctx->stream,
                        reinterpret_cast<const unsigned*>(work + p.l.records), reinterpret_cast<const unsigned*>(work + p.l.start),
                        p.b, p.l.nbricks, grid);
   }
@@ -1709,26 +1506,22 @@ int deposit_assign_field_run(vps_ctx* ctx, const void* pos_v, const float* vel, 
   const int span = nx + ORDER - 1 >= N ? 0x7fffffff : nx + ORDER - 1;     // (the whole ring: every particle passes)
   const size_t lds = tile_bytes(4, b.cells, quantity);       // (five channels for the second-moment quantities)
   if (int rcl = check_second_moment_tile(ctx, quantity, lds)) return rcl;      // before anything is enqueued
-  const int rc = assign_sort(ctx, AssignRhovPayload<F, ORDER>{pos, vel, rho, lcell},
-                             [&](auto k) { return AssignSlabKeyOf<F, decltype(k), ORDER>{pos, lcell, (double)N, b, xlo, span}; },
-                             np, p, work);
-  if (rc) return rc;
+  {
+    vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
+    const int rc = sort_records(ctx, [&](auto k) { return AssignKeyOf<F, decltype(k), ORDER, SlabWindow>{pos, lcell, (double)N, b, {xlo, span}}; },
+                                AssignPayload<F, 4, true, ORDER>{pos, vel, rho, lcell}, (long long)np, p.l, work);
+    if (rc) return rc;
+  }
   const float vol = (float)(lcell * lcell * lcell);
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
     const int ix_lo = x0 / b.bx, ix_hi = (x0 + nx - 1) / b.bx;
     const long long per_x = (long long)b.nby * b.nbz;
     const long long first = ix_lo * per_x, nbricks = (ix_hi - ix_lo + 1) * per_x;
-    long long per_cu = (long long)(ctx->lds_per_cu / (lds ? lds : 1));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    long long grid_wg = (long long)ctx->num_cu * per_cu;
-    if (grid_wg > nbricks) grid_wg = nbricks;
     const int rcq = dispatch_quantity<true>(quantity, [&](auto q) -> int {
       auto kern = assign_field_kernel<ORDER, decltype(q)::value>;
-      if (lds > 64 * 1024)
-        VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid_wg), dim3(256), lds, ctx->stream,
+      if (int rcl = raise_lds_limit(ctx, kern, lds)) return rcl;
+      hipLaunchKernelGGL(kern, dim3(brick_launch_grid(ctx, lds, nbricks)), dim3(256), lds, ctx->stream,
                          reinterpret_cast<const unsigned*>(work + p.l.records), reinterpret_cast<const unsigned*>(work + p.l.start),
                          b, first, nbricks, x0, nx, flags, brick_par(ctx, decltype(q)::value, vol), fields);
       return VPS_OK;
@@ -1964,7 +1757,7 @@ int vps_deposit_plan(vps_ctx* ctx, int64_t np, int C, int N, int x0, int nx, int
   out[8] = g.gshift;
   out[9] = g.ngroups;
   out[10] = g.nchunks;
-  out[11] = l.two_level && sort_staged() && lds_staged <= ctx->lds_per_cu;   // (sort_into_buckets' rule)
+  out[11] = l.two_level && sort_staged() && lds_staged <= ctx->lds_per_cu;   // (sort_records' rule)
   out[12] = (int64_t)lds_staged;
   out[13] = l.recompute;
   out[14] = l.cap_in;
@@ -2106,7 +1899,7 @@ int vps_deposit_assign_plan(vps_ctx* ctx, int64_t np, int C, int N, int order, i
   out[8] = p.l.two_level;
   out[9] = p.l.wide_keys;
   out[10] = C + 7;
-  out[11] = p.l.two_level && sort_staged() && lds_staged <= ctx->lds_per_cu;   // (assign_sort's rule)
+  out[11] = p.l.two_level && sort_staged() && lds_staged <= ctx->lds_per_cu;   // (sort_records' rule)
   out[12] = p.l.geom.gshift;
   out[13] = (int64_t)most[0] * most[1] * most[2];
   return VPS_OK;

@@ -106,7 +106,7 @@ def test_cli_gridding_and_deconvolve(po, capsys):
 
 
 def _key_keeps(c0x, N, x0, nx, order):
-    """The slab window of the sort key (csrc/deposit.hip: AssignSlabKeyOf), restated: a particle with base cell c0x is kept
+    """The slab window of the sort key (csrc/deposit.hip: SlabWindow), restated: a particle with base cell c0x is kept
     unless ((c0x - (x0 - (order - 1))) mod N) >= nx + order - 1; with nx + order - 1 >= N every particle is kept."""
     span = nx + order - 1
     if span >= N:
@@ -116,7 +116,7 @@ def _key_keeps(c0x, N, x0, nx, order):
 
 @pytest.mark.parametrize("assignment", ["cic", "tsc"])
 def test_key_window_keeps_exactly_the_particles_with_a_target_row_in_the_slab(assignment):
-    """Guards the FORMULA of the slab window, not the kernel: `_key_keeps` restates AssignSlabKeyOf's test in numpy and is held
+    """Guards the FORMULA of the slab window, not the kernel: `_key_keeps` restates SlabWindow's test in numpy and is held
     against the target rows small_ref gives, so it says the rule documented in the header and DESIGN.md is the right one.  It
     does not read the device code (it passes with or without it); that the kernel applies this rule is what the per-slab
     lattice cases of tests/test_gpu_assign_field.py show."""
