@@ -542,7 +542,24 @@ int vps_fft_y(vps_ctx* ctx, int N, int nx, const void* zimg_dev, int G, int nchu
  * mode 4: transform and discard (a timing aid: the pass without its epilogue).
  * mode 1: write the transformed lines to out_dev[i][kx] (complex64, contiguous).
  * mode 2: out_dev[i][kx] (float32) += |F|^2, no binning (component sums of
- *         _vector_power, interp.py:1386).                                           */
+ *         _vector_power, interp.py:1386).
+ * Real-space two-point statistics (an addition within ABI 13: no new symbol).  The power grid of a real field is real and
+ * even, so its FORWARD transform is N^3 times the autocorrelation: no inverse transform exists or is needed.  Three modes,
+ * whole lines of whole grids only -- nseg must be 1, else VPS_ERR_ARG before anything is enqueued:
+ * mode 5: as mode 2, but out_dev is the BASE of a full [N][N][N] float32 grid indexed [kz][ky][kx], whatever line0 / kz0:
+ *         the line (ky, kz), 0 <= kz <= N/2, adds |F(kx)|^2 at [kz][ky][kx] and, for 0 < kz < N/2, the same value at the
+ *         Hermitian partner [N-kz][(N-ky)%N][(N-kx)%N].  The planes kz = 0 and N/2 write no mirror: their partners are
+ *         lines of the same plane.  One writer per element and call, plain +=: the caller zeroes the grid, the components
+ *         of a vector field accumulate over calls.  The result is a real field that vps_fft_zy accepts.  Like modes 1 and
+ *         2 it reads every row: run the y pass outside a binning-only scope.  A kz range outside 0..N/2: VPS_ERR_ARG.
+ * mode 6: the binning of mode 0 with w*Re F(kx) accumulated into psum_dev where mode 0 accumulates w*|F|^2, and w into
+ *         nsample_dev; the imaginary part is ignored.  Tables (vps_set_binning: for a correlation function the axis table
+ *         is fl(r*r), r = Lcell * min(i, N - i), the thresholds those of the r edges), multiplicity w, shell decision
+ *         (vps_binning_mode), +-kx / +-ky pairing, row cut and float64 accumulation are those of mode 0.
+ * mode 7: as mode 6, shell sums only (nsample_dev untouched), as mode 3 is to mode 0.
+ *         Modes 6 / 7 return VPS_ERR_ARG before anything is enqueued while a window is set (vps_set_window: a k-space
+ *         window on an r lattice is a caller's error) and for a null accumulator.  vps_fft_x_bin*, vps_spectrum_zimages
+ *         and the chunked exchange do not take modes 5..7.  Any other mode: VPS_ERR_ARG ("mode must be 0..7").   */
 int vps_fft_x(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0,
               const void* in_dev, int nseg, int64_t seg_stride, int mode,
               double* psum_dev, unsigned long long* nsample_dev, void* out_dev);

@@ -431,6 +431,9 @@ static int fft_x_impl(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz
   if (int bad = check_fft_size(ctx, N)) return bad;
   if (nlines < 0 || !in_dev) return vps_fail(ctx, VPS_ERR_ARG, "bad line count / null input");
   if (nseg < 1 || N % nseg) return vps_fail(ctx, VPS_ERR_ARG, "nseg=%d must divide N", nseg);
+  // modes 5 (|F|^2 into the full Hermitian grid) and 6 / 7 (signed binning of Re F) take whole lines of whole grids
+  const bool realbin = mode == 6 || mode == 7;
+  if ((mode == 5 || realbin) && nseg != 1) return vps_fail(ctx, VPS_ERR_ARG, "mode %d: nseg must be 1", mode);
   if (nlines == 0) return VPS_OK;
   vps_fft_tables tx;
   int rc = vps_fft_get_tables(ctx, N, &tx);
@@ -455,11 +458,14 @@ static int fft_x_impl(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz
   p.kz_step = kz_step;
   if (ptab && (line0 != 0 || nlines % N || (mode != 0 && mode != 3)))
     return vps_fail(ctx, VPS_ERR_ARG, "chunk planes: whole planes from line 0, binning modes only");
-  const bool binning = mode == 0 || mode == 3;
+  const bool binning = mode == 0 || mode == 3 || realbin;
+  const bool counting = mode == 0 || mode == 6;
   int fastmode = 0;
   if (binning) {
     if (ctx->bin_N != N || !ctx->d_k2) return vps_fail(ctx, VPS_ERR_ARG, "vps_set_binning(N=%d) has not been called", N);
-    if (!psum_dev || (mode == 0 && !nsample_dev)) return vps_fail(ctx, VPS_ERR_ARG, "null accumulator");
+    if (!psum_dev || (counting && !nsample_dev)) return vps_fail(ctx, VPS_ERR_ARG, "null accumulator");
+    if (realbin && ctx->d_win)
+      return vps_fail(ctx, VPS_ERR_ARG, "mode %d bins a real-space lattice: a k-space window is set (vps_set_window(NULL) first)", mode);
     const long long maxline = line0 + nlines - 1;
     if (kz0 + (int)(maxline / N) * kz_step > N / 2) return vps_fail(ctx, VPS_ERR_ARG, "kz range exceeds N/2");
     p.k2 = ctx->d_k2;
@@ -478,13 +484,16 @@ static int fft_x_impl(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz
     fastmode = !ctx->bin_fast ? 0 : (ctx->bin_int && ctx->d_nthr && vps_option("no_int_binning", 0) == 0) ? 2 : 1;
     p.psumc = psumc_dev;
     if (psumc_dev && ncomp != 3) return vps_fail(ctx, VPS_ERR_ARG, "Helmholtz decomposition: ncomp must be 3");
-  } else if (mode == 1 || mode == 2) {
+  } else if (mode == 1 || mode == 2 || mode == 5) {
     if (!out_dev) return vps_fail(ctx, VPS_ERR_ARG, "null output");
+    // mode 5 addresses the full grid by (ky, kz): every plane of the call and its partner N - kz must lie inside it
+    if (mode == 5 && (line0 < 0 || kz0 < 0 || kz0 + (line0 + nlines - 1) / N > N / 2))
+      return vps_fail(ctx, VPS_ERR_ARG, "mode 5: kz range exceeds 0..N/2");
   } else if (mode != 4) {
-    return vps_fail(ctx, VPS_ERR_ARG, "mode must be 0..4");
+    return vps_fail(ctx, VPS_ERR_ARG, "mode must be 0..7");
   }
-  // (modes 0 and 3 are the kernel's binning MODE 0, with and without the shell counts)
-  return route_x(ctx, N, binning ? 0 : mode, mode == 0, p, fastmode, binning && psumc_dev);
+  // (modes 0 and 3 are the kernel's binning MODE 0, with and without the shell counts; 6 and 7 its signed variant)
+  return route_x(ctx, N, realbin ? 6 : (binning ? 0 : mode), counting, p, fastmode, binning && psumc_dev);
 }
 
 int vps_fft_x(vps_ctx* ctx, int N, int64_t nlines, int64_t line0, int kz0, const void* in_dev,

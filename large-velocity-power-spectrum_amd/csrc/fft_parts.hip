@@ -75,6 +75,14 @@ int FftPart<PART>::x(vps_ctx* ctx, int NC, int mode, int count, const XParams& p
     } else {
       VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, false, true>(ctx, p, fast)));
     }
+  } else if (mode == 6) {   // the signed binning of Re F (vps_fft_x modes 6 / 7)
+    if (count) {
+      VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, true, false, true>(ctx, p, fast)));
+    } else {
+      VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, false, false, true>(ctx, p, fast)));
+    }
+  } else if (mode == 5) {
+    VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 5>(ctx, p)));
   } else if (mode == 0 && count) {
     VPS_DISPATCH_NC(NC, (rc = launch_x<NC_, 0, true>(ctx, p, fast)));
   } else if (mode == 0) {

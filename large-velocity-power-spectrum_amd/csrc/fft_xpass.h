@@ -41,7 +41,12 @@ template <int NC>
 constexpr int x_cimg_pitch(bool fast) {   // floats per line of the HELM image: index k + k / CH, k < NC
   return NC + NC / (fast ? PlanInfo<NC>::RL / 2 : PlanInfo<NC>::RL) + 1;
 }
-template <int NC, int T, int MODE, bool SEG, bool COUNT, int FASTMODE, bool HELM = false>
+// REALB (MODE 0, one component): the signed binning of vps_fft_x modes 6 / 7 -- Re F(kx) goes into the line's image where
+// |F|^2 goes otherwise (the imaginary part is dropped); tables, multiplicities, shell decision, pairing, row cut and the
+// float64 LDS atomics are the ones below, untouched.  A sum of values is binned, so +-kx and +-ky still share one atomic.
+// MODE 5: |F|^2 ADDED into a full Hermitian [N][N][N] float32 grid, the line (ky, kz) at [kz][ky][:] and, for 0 < kz < N/2,
+// once more at its partner [N-kz][(N-ky)%N][(N-kx)%N]; the planes kz = 0 and N/2 hold their partners as lines of their own.
+template <int NC, int T, int MODE, bool SEG, bool COUNT, int FASTMODE, bool HELM = false, bool REALB = false>
 __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG>() ? (HELM ? 2 : 3) : 1)) fft_x_pass(const XParams p) {
   typedef PlanInfo<NC> PI;
   constexpr bool FAST = FASTMODE != 0, INTB = FASTMODE == 2, TWREG = x_twreg<NC, FASTMODE, SEG>();
@@ -317,6 +322,26 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
 #pragma unroll
         for (int i = 0; i < RL; ++i) o[out_index<NC>(l, i)] += v[i].x * v[i].x + v[i].y * v[i].y;
       }
+    } else if constexpr (MODE == 5) {
+      // p.out is the BASE of the full grid, whatever line0 / kz0 (fft_x_impl has checked 0 <= kz <= N/2).  For a register slot
+      // i the lanes of a line hold consecutive kx (out_index = l + const): the direct store is one ascending run of 4 L bytes
+      // per line, the mirrored one the same run of the partner line walked downwards -- the same cache lines, fully covered
+      // by one wave instruction either way.  Every element has one writer: a plain read-modify-write.
+      if (live_cur) {
+        const long long g = p.line0 + li_cur;
+        const int ky = (int)(g % NC), kz = p.kz0 + (int)(g / NC);
+        float* base = reinterpret_cast<float*>(p.out);
+        float* o = base + ((long long)kz * NC + ky) * NC;
+        const bool mir = kz > 0 && 2 * kz < NC;
+        float* m = mir ? base + ((long long)(NC - kz) * NC + (ky ? NC - ky : 0)) * NC : o;
+#pragma unroll
+        for (int i = 0; i < RL; ++i) {
+          const int kx = out_index<NC>(l, i);
+          const float a = v[i].x * v[i].x + v[i].y * v[i].y;
+          o[kx] += a;
+          if (mir) m[kx ? NC - kx : 0] += a;
+        }
+      }
     } else {
       // Shell sums.  |F|^2 goes through LDS once so that every lane gets a CONTIGUOUS chunk
       // of RL kx values: along kx the shell index moves monotonically (per half line), so a
@@ -339,7 +364,9 @@ __global__ void __launch_bounds__(T* PlanInfo<NC>::L, (x_twreg<NC, FASTMODE, SEG
         fft_from_regs<NC, WSYNC, TWREG>(v, line, tw, lc, twr);
 #pragma unroll
         for (int i = 0; i < RL; ++i) {
-          const float a = v[i].x * v[i].x + v[i].y * v[i].y;
+          float a;
+          if constexpr (REALB) a = v[i].x;
+          else a = v[i].x * v[i].x + v[i].y * v[i].y;
           pacc[i] = (c == 0) ? a : pacc[i] + a;
         }
         if constexpr (HELM) {
@@ -582,9 +609,11 @@ __global__ void __launch_bounds__(256)
   if (part_cnt && c) atomicAdd(&nsample[i], c);
 }
 
-template <int NC, int MODE, bool COUNT = false, bool HELM = false>
+template <int NC, int MODE, bool COUNT = false, bool HELM = false, bool REALB = false>
 int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 general shell walk, 1 mirrored kx (float64), 2 integer shells
   static_assert(!HELM || MODE == 0, "the Helmholtz decomposition is a binning variant");
+  static_assert(!REALB || (MODE == 0 && !HELM), "the signed binning is a one-component binning variant");
+  constexpr bool NOSEG = REALB || MODE == 5;   // whole lines only: no segment variants are built for them (fft_x_impl refuses)
   XParams p = p_in;
   constexpr int T = xpass_T<NC>();
   typedef PlanInfo<NC> PI;
@@ -600,10 +629,18 @@ int launch_x(vps_ctx* ctx, const XParams& p_in, int fast = 0) {   // fast: 0 gen
   if (seg && x_seg_min_len<NC>() > 1 && (p.seg_shift < 0 || p.seglen < x_seg_min_len<NC>()))   // (callers check vps_x_max_ranks first)
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "x pass: lines of %d points in segments of %d (more than %d ranks)", NC, p.seglen,
                     NC / x_seg_min_len<NC>());
-  auto kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 0, HELM> : fft_x_pass<NC, T, MODE, false, COUNT, 0, HELM>;
+  if (NOSEG && seg) return vps_fail(ctx, VPS_ERR_ARG, "x pass: this mode takes whole lines (nseg = 1)");
+  auto kern = fft_x_pass<NC, T, MODE, false, COUNT, 0, HELM, REALB>;
+  if constexpr (!NOSEG) {
+    if (seg) kern = fft_x_pass<NC, T, MODE, true, COUNT, 0, HELM>;
+  }
   if constexpr (MODE == 0 && NC >= 32) {
-    if (fast == 1) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 1, HELM> : fft_x_pass<NC, T, MODE, false, COUNT, 1, HELM>;
-    if (fast == 2) kern = seg ? fft_x_pass<NC, T, MODE, true, COUNT, 2, HELM> : fft_x_pass<NC, T, MODE, false, COUNT, 2, HELM>;
+    if (fast == 1) kern = fft_x_pass<NC, T, MODE, false, COUNT, 1, HELM, REALB>;
+    if (fast == 2) kern = fft_x_pass<NC, T, MODE, false, COUNT, 2, HELM, REALB>;
+    if constexpr (!NOSEG) {
+      if (fast == 1 && seg) kern = fft_x_pass<NC, T, MODE, true, COUNT, 1, HELM>;
+      if (fast == 2 && seg) kern = fft_x_pass<NC, T, MODE, true, COUNT, 2, HELM>;
+    }
   }
   if (lds > 64 * 1024)
     VPS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),

@@ -233,6 +233,41 @@ def sqrt_thresholds(edges):
     return thr
 
 
+def binning_tables(axis, edges):
+    """The arguments of vps_set_binning -- (N, fl(a*a) axis table, thresholds, first edge, 1 / spacing) -- for uniform
+    `edges` on a lattice whose axis values are `axis`: k = 2 pi fftfreq(N, Lcell) for a spectrum (`k_axis`), the lag
+    r = Lcell min(i, N - i) for a correlation function (`r_axis`).  The binning kernel does not care which."""
+    axis = np.asarray(axis, dtype=np.float64)
+    edges = np.asarray(edges, dtype=np.float64)
+    spacing = (edges[-1] - edges[0]) / (len(edges) - 1)
+    return (len(axis), axis * axis, sqrt_thresholds(edges), float(edges[0]), 1.0 / spacing)
+
+
+def r_axis(Lbox, Nsize):
+    """Lag of lattice index i along one axis of a periodic box, Lcell * min(i, N - i): even in i and non-decreasing on
+    [0, N/2], like |k| of `k_axis` -- the mirrored shell decisions of the binning x pass hold for it unchanged."""
+    Lcell = Lbox / float(Nsize)
+    i = np.arange(int(Nsize))
+    return Lcell * np.minimum(i, int(Nsize) - i).astype(np.float64)
+
+
+def radial_edges(Lbox, Nsize, rmin=None, rmax=None, rres=None):
+    """Uniform r edges rmin + j rres, j = 0 .. nb, the last one <= rmax.  Defaults rmin = 0, rres = Lcell, rmax = L/2: the
+    edges j Lcell, j = 0 .. N/2, the same float64 products as the lattice lags -- the first bin [0, Lcell) holds r = 0 alone
+    and the last is right-closed at L/2 (numpy.histogram's rule, `sqrt_thresholds`).  rmax up to sqrt(3) L/2 reaches every
+    lattice point."""
+    Lcell = Lbox / float(Nsize)
+    rmin = 0.0 if rmin is None else float(rmin)
+    rres = Lcell if rres is None else float(rres)
+    rmax = Lcell * (int(Nsize) // 2) if rmax is None else float(rmax)
+    if not (rres > 0 and rmin >= 0 and rmax > rmin):
+        raise ValueError("need 0 <= rmin < rmax and rres > 0 (got %r, %r, %r)" % (rmin, rmax, rres))
+    nb = int(np.floor((rmax - rmin) / rres + 1e-9))
+    if nb < 1:
+        raise ValueError("rres = %r leaves no bin between rmin = %r and rmax = %r" % (rres, rmin, rmax))
+    return rmin + rres * np.arange(nb + 1)
+
+
 # --------------------------------------------------------------------------- #
 # kernel set backed by libvps_hip.so
 # --------------------------------------------------------------------------- #
@@ -896,6 +931,50 @@ class HipKernels:
                                               self._ptr(out)))
         return out
 
+    def fft_x_mode(self, lines, N, nlines, line0, kz0, mode, psum=None, nsample=None, out=None, nseg=1, seg_stride=0):
+        """vps_fft_x in any of its modes (include/vps_hip.h) on complex64 lines; the accumulators / output a mode does not take
+        stay None."""
+        self._stream()
+        self._chk(self.lib.vps_fft_x(self.ctx, int(N), int(nlines), int(line0), int(kz0), self._ptr(lines, torch.complex64),
+                                     int(nseg), int(seg_stride), int(mode), self._ptr(psum, torch.float64),
+                                     self._ptr(nsample, torch.int64), self._ptr(out)))
+
+    def _zy_into_power_workspace(self, field, N):
+        """z and y pass of a whole [N,N,N] float32 field inside the power workspace: -> (spec [N/2,N,N], nyq [N,N]) views of
+        its second half (the layout vps_power_grid uses)."""
+        half = int(self.lib.vps_fft_workspace_bytes(N, N))
+        work = self.workspace("power", self.lib.vps_power_workspace_bytes(N))
+        nspec = (N // 2) * N * N
+        img = work[half: 2 * half].view(torch.complex64)
+        spec, nyq = img[:nspec].view(N // 2, N, N), img[nspec: nspec + N * N].view(N, N)
+        self._chk(self.lib.vps_fft_zy(self.ctx, N, N, self._ptr(field, torch.float32), self._ptr(spec), self._ptr(nyq),
+                                      self._ptr(work)))
+        return spec, nyq
+
+    def power_grid_full(self, fields, N):
+        """sum over fields of |F|^2 on the FULL Hermitian grid [kz][ky][kx], N^3 float32 (vps_fft_x mode 5): a real, even field
+        that the real-input z pass takes -- its forward transform is N^3 times the autocorrelation.  Every row is read: the y
+        passes run outside any binning-only scope."""
+        self._stream()
+        self._chk(self.lib.vps_set_bin_only(self.ctx, 0))
+        out = self.zeros((N, N, N), torch.float32)
+        for f in fields:
+            spec, nyq = self._zy_into_power_workspace(f, N)
+            self.fft_x_mode(spec, N, (N // 2) * N, 0, 0, 5, out=out)
+            self.fft_x_mode(nyq, N, N, 0, N // 2, 5, out=out)
+        return out
+
+    def bin_real(self, grid, N, psum, nsample):
+        """Transform the real [N,N,N] float32 `grid` and ADD the shell sums of w Re F into psum (float64) and w into nsample
+        (int64) with the tables set last (vps_fft_x mode 6; w the Hermitian multiplicity of the kz plane).  The y pass skips
+        the rows no shell of those tables holds, as the spectrum's binning does."""
+        self._stream()
+        with self.binning_only():
+            spec, nyq = self._zy_into_power_workspace(grid, N)
+        self.fft_x_mode(spec, N, (N // 2) * N, 0, 0, 6, psum=psum, nsample=nsample)
+        self.fft_x_mode(nyq, N, N, 0, N // 2, 6, psum=psum, nsample=nsample)
+        return psum, nsample
+
     def pair_k(self, kx, ky, kz):
         self._stream()
         ax = [np.ascontiguousarray(a, dtype=np.float64) for a in (kx, ky, kz)]
@@ -1122,11 +1201,8 @@ class PowerPipeline:
         self.kres = self.kmin if kres is None else kres
         self.centers, self.edges = bin_edges(self.kmin, self.kmax, self.kres, flavour)
         self.nbins = len(self.centers)
-        ks = k_axis(self.Lbox, self.N)
-        self.k2 = ks * ks
-        self.thr = sqrt_thresholds(self.edges)
-        spacing = (self.edges[-1] - self.edges[0]) / self.nbins
-        self._binning = (self.N, self.k2, self.thr, float(self.edges[0]), 1.0 / spacing)
+        self._binning = binning_tables(k_axis(self.Lbox, self.N), self.edges)
+        self.k2, self.thr = self._binning[1], self._binning[2]
         self.const = (self.Lbox / (2 * np.pi)) ** 1.5 / self.N ** 3   # interp.py:1381
         # deconvolve = "ngp" | "cic" | "tsc": divide every |F(k)|^2 by the assignment window W(k)^2 while binning
         self.window = None if deconvolve is None else window_inv2_axis(self.N, deconvolve)
@@ -1507,3 +1583,72 @@ class PowerPipeline:
         tab = self.finish(psum, nsample)
         tab[:, 1] *= 4 * np.pi * tab[:, 0] ** 2   # interp.py:590 / parallel_optimized.py:434
         return tab
+
+
+class CorrelationPipeline:
+    """xi(r) = <f(x) . f(x + r)> of real fields on a WHOLE N^3 grid of one GPU, binned in shells of the lag r.
+
+    xi is the transform of the power grid |F|^2, and that grid is real and even: a second FORWARD transform gives it (the
+    inverse would differ by the sign of an imaginary part that is zero).  So the three passes and the exact shell histogram
+    of the spectrum serve unchanged, with the lags r = Lcell min(i, N - i) as the axis table (`r_axis`, `binning_tables`).
+    Like `PowerPipeline` the object owns its tables and uploads them (window off) before it bins: it leaves no state that a
+    spectrum computed afterwards could pick up.  x-slabs and several GPUs are out of scope: `comm` with more than one rank
+    raises."""
+
+    def __init__(self, Nsize, Lbox, kernels=None, rmin=None, rmax=None, rres=None, comm=None):
+        self.N = int(Nsize)
+        self.Lbox = float(Lbox)
+        self.Lcell = self.Lbox / self.N
+        if comm is not None and getattr(comm, "world", 1) > 1:
+            raise Exception("the correlation function takes whole grids on one GPU: no x-slabs (%d ranks)" % comm.world)
+        self.k = kernels if kernels is not None else default_kernels()
+        if not self.k.fft_supported(self.N):
+            raise Exception("Nsize=%d is not supported by the device FFT (powers of two 16..4096, 96, 192, 384, 768, 1536, 250, 500, 1000, 2000)" % self.N)
+        self.edges = radial_edges(self.Lbox, self.N, rmin, rmax, rres)
+        self.centers = 0.5 * (self.edges[:-1] + self.edges[1:])      # bin centres, as the k column of a spectrum
+        self.nbins = len(self.centers)
+        self._binning = binning_tables(r_axis(self.Lbox, self.N), self.edges)
+
+    def prepare(self):
+        self.k.set_binning(*self._binning)
+        self.k.set_window(self.N, None)       # (a k-space window on the r lattice is refused by the library)
+
+    def correlation(self, fields, subtract_mean=True):
+        """-> (table [nbins, 3] of r, xi, nsample; xi0), all float64 on the host.  `fields`: the components ([N,N,N] float32
+        device tensors); a vector gives the trace sum_c xi_cc.
+        The power grid's float64 sum is xi(0) N^6; its k = 0 entry (|mean|^2 N^6) is set to 0 and the grid scaled by an exact
+        power of two so that it sums to at most 1: every value of the second transform is then at most 1 in magnitude,
+        whatever the caller's units, and the scale is undone exactly in float64.  A first bin that holds r = 0 alone takes the
+        float64 sum itself, so that xi[0] is xi0 bit for bit; shells without a lattice point hold 0."""
+        import math
+        N, k = self.N, self.k
+        grid = k.power_grid_full(fields, N)
+        p0 = float(grid[0, 0, 0])
+        grid[0, 0, 0] = 0
+        body = float(grid.sum(dtype=torch.float64))
+        if not math.isfinite(body) or not math.isfinite(p0):
+            raise Exception("the power grid left the float32 range: rescale the field")
+        e = math.frexp(body)[1] if body > 0 else 0          # body = m 2^e, 1/2 <= m < 1
+        for part in (-e // 2, -e - (-e // 2)):              # (two exact factors: 2^-e itself may leave the float32 range)
+            if part:
+                grid.mul_(math.ldexp(1.0, part))
+        self.prepare()
+        buf = k.zeros((2 * self.nbins,), torch.float64)
+        psum, nsample = buf[:self.nbins], buf[self.nbins:].view(torch.int64)
+        k.bin_real(grid, N, psum, nsample)
+        host = buf.cpu()
+        ps = host[:self.nbins].numpy()
+        ns = host[self.nbins:].view(torch.int64).numpy()
+        n6 = float(N) ** 6
+        with np.errstate(invalid="ignore", divide="ignore"):
+            xi = np.ldexp(ps / ns, e) / n6
+        xi[ns == 0] = 0
+        xi0 = body / n6
+        if self.edges[0] <= 0 and ns[0] == 1:
+            xi[0] = xi0
+        if not subtract_mean:
+            xi[ns > 0] += p0 / n6
+            xi0 += p0 / n6
+            if self.edges[0] <= 0 and ns[0] == 1:
+                xi[0] = xi0
+        return np.column_stack((self.centers, xi, ns.astype(np.float64))), xi0

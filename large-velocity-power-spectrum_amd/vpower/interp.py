@@ -22,15 +22,15 @@ import torch
 
 try:  # `from vpower.interp import *` and the reference's bare `import interp` both work
     from . import device as _dev
-    from .spctrm import PowerSpectrum
+    from .spctrm import CorrelationFunction, PowerSpectrum
 except ImportError:  # pragma: no cover
     import device as _dev
-    from spctrm import PowerSpectrum
+    from spctrm import CorrelationFunction, PowerSpectrum
 
 __all__ = [
     "load_snapshot", "GasParticles", "BoxField", "deposit_to_grid", "ann_interpolate",
     "make_grid_coords", "check_conservation", "_vector_power", "_scalar_power", "_pair_power",
-    "_hist_sample", "PowerSpectrum", "REFERENCE_COMPAT",
+    "_hist_sample", "PowerSpectrum", "CorrelationFunction", "REFERENCE_COMPAT",
 ]
 
 # Reproduce reference defects that change numbers:
@@ -586,6 +586,45 @@ class BoxField:
         else:
             tabs = pipe.spectrum_helmholtz(self._fields(k, qcode if quantity == "weighted_velocity" else quantity))
         return tuple(PowerSpectrum(t) for t in tabs)
+
+    def _real_space_fields(self, k, quantity, qcode):
+        """The real-space fields of a quantity on the device, by the route `spctrm` takes for this kind of field -- except that
+        a particle-backed NGP field, whose spectrum never builds a grid, deposits the quantity's fields here."""
+        src = getattr(self, "_src", None)
+        if src is not None:
+            return self._assigned_fields(k, src, quantity, qcode)
+        flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
+        nn = getattr(self, "_nn_src", None)
+        if nn is not None and self._nn_spectra == 0:
+            self._nn_spectra = 1        # (as spctrm: the search writes this quantity's fields directly)
+            f, _ = k.nn_resample_quantity(nn[0], nn[1], (nn[2], nn[2], nn[2]), 0, self.Nsize, self.Lcell, qcode, flags)
+            return [f[i] for i in range(f.shape[0])]
+        return self._fields(k, qcode if quantity in ("weighted_velocity", "density") else quantity)
+
+    def correlation(self, quantity="velocity", rmin=None, rmax=None, rres=None, density_weight=None,
+                    subtract_mean=True) -> CorrelationFunction:
+        """Two-point correlation function xi(r) = <f(x) . f(x + r)> of a quantity, binned in shells of the lag r (extension; the
+        reference has no real-space statistic): the average runs over all N^3 cells x and, per shell, over every lattice lag
+        r = Lcell (min(i, N - i), ...) of the periodic box whose length falls into the shell.  Vector quantities give the
+        trace sum_c xi_cc.  Every quantity of `spctrm` is taken, on every kind of field, with the same refusals by name.
+        Computed through the FFT passes in O(N^3 log N): power grid on the full Hermitian lattice, a second forward transform,
+        the exact shell histogram of `spctrm` on the r lattice.  Default shells: edges j Lcell, j = 0 .. N/2 -- the first holds
+        r = 0 alone, the last is right-closed at L/2; rmin / rmax / rres give uniform edges rmin + j rres <= rmax instead
+        (rmax = sqrt(3) L/2 reaches every lag).  subtract_mean=False keeps |<f>|^2 in xi.
+        Whole grids on one GPU; there is no window deconvolution for xi."""
+        quantity, qcode = _dev.resolve_quantity(quantity, density_weight)
+        if _dev.needs_second_moment(qcode):
+            self._second_moment_source(quantity)     # (raises by name on a field without particles, before any device work)
+        k = _kernels()
+        pipe = _dev.CorrelationPipeline(self.Nsize, self.Lbox, kernels=k, rmin=rmin, rmax=rmax, rres=rres)
+        table, xi0 = pipe.correlation(self._real_space_fields(k, quantity, qcode), subtract_mean=subtract_mean)
+        return CorrelationFunction(table, xi0)
+
+    def structure_function(self, quantity="velocity", rmin=None, rmax=None, rres=None, density_weight=None,
+                           subtract_mean=True) -> np.ndarray:
+        """Second-order structure function S2(r) = <|f(x + r) - f(x)|^2> = 2 (xi(0) - xi(r)) on the shells of `correlation`
+        (same arguments): an (nbins, 3) float64 table r, S2, Nsample.  The mean drops out of S2 either way."""
+        return self.correlation(quantity, rmin, rmax, rres, density_weight, subtract_mean).structure_function()
 
     # -- diagnostics (interp.py:639-666) ----------------------------------------------
     def _totals(self):

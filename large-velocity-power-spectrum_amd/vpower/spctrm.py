@@ -152,6 +152,65 @@ class PowerSpectrum:
         return PowerSpectrum(np.loadtxt(filename))
 
 
+class CorrelationFunction:
+    """Columns r, xi, Nsample of a binned two-point correlation function xi(r) = <f(x) . f(x + r)> (extension; the reference
+    has no real-space statistic): r the bin centres, formed like the k column of a `PowerSpectrum`, Nsample the lattice
+    lags per shell.  `xi0` is xi at zero lag, the float64 mean of |f|^2 -- the first bin holds it alone when the edges start
+    at 0 (the default).  `structure_function()` is the second-order structure function of the same field.
+    Indexing, iteration, `data()`, `copy()` and the pickle / text files work as for a `PowerSpectrum`."""
+
+    columns = ("r", "xi", "Nsample")
+
+    def __init__(self, table, xi0) -> None:
+        table = np.asarray(table, dtype=np.float64)
+        self.r = table[:, 0]
+        self.xi = table[:, 1]
+        self.Nsample = table[:, 2]
+        self.xi0 = float(xi0)
+
+    def data(self):
+        return np.stack([self.r, self.xi, self.Nsample], axis=1)
+
+    def __len__(self):
+        return len(self.r)
+
+    def __iter__(self):
+        return iter(self.data())
+
+    def __getitem__(self, index):
+        return self.data()[index]
+
+    def copy(self):
+        return CorrelationFunction(self.data(), self.xi0)
+
+    def structure_function(self):
+        """(nbins, 3) float64 table r, S2 = <|f(x + r) - f(x)|^2> = 2 (xi(0) - xi(r)), Nsample; shells without a lattice
+        point hold 0.  S2 of the r = 0 bin is exactly 0."""
+        s2 = 2.0 * (self.xi0 - self.xi)
+        s2[self.Nsample == 0] = 0
+        return np.stack([self.r, s2, self.Nsample], axis=1)
+
+    def save(self, run_output_dir) -> None:
+        with open(os.path.join(run_output_dir, "correlation.pkl"), "wb") as fh:
+            pickle.dump(self, fh)
+
+    @staticmethod
+    def load(run_output_dir):
+        return load_spectrum(os.path.join(run_output_dir, "correlation.pkl"))
+
+    def savetxt(self, filename) -> None:
+        """The three columns, with xi0 in the header line (float64 round trip: repr)."""
+        np.savetxt(filename, self.data(), header="xi0 %r" % self.xi0)
+
+    @staticmethod
+    def loadtxt(filename):
+        with open(filename) as fh:
+            head = fh.readline().split()
+        if len(head) != 3 or head[:2] != ["#", "xi0"]:
+            raise Exception("%s is not a CorrelationFunction table (no '# xi0 <value>' header)" % filename)
+        return CorrelationFunction(np.loadtxt(filename, ndmin=2), float(head[2]))
+
+
 class SpectrumList:
     """Sub-spectra keyed by their beta vector (spctrm.py:252-316)."""
 
