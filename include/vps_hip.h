@@ -83,7 +83,10 @@ enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                     VPS_LOG_DENSITY = 6 /* ABI 11: the scalar s = ln rho */,
                     /* an addition within ABI 13, vps_deposit_field ONLY: scalars of the second moment S2 = sum w rho_p |v_p|^2 of
                        a cell's contributions, see "Sub-grid velocity dispersion" below */
-                    VPS_TOTAL_ENERGY = 7, VPS_SUBGRID_ENERGY = 8, VPS_DISPERSION = 9 };
+                    VPS_TOTAL_ENERGY = 7, VPS_SUBGRID_ENERGY = 8, VPS_DISPERSION = 9,
+                    /* an addition within ABI 13, vps_deposit_field ONLY: the six components of that second moment as a tensor,
+                       see "Sub-grid stress tensor" below */
+                    VPS_SUBGRID_STRESS = 10, VPS_DISPERSION_TENSOR = 11 };
 /* flags for vps_field_algebra */
 #define VPS_FLAG_REFERENCE_MOMENTUM_BUG 1 /* py=pz=vx*mass as interp.py:523-525 */
 #define VPS_FLAG_INPUT_IS_VM 2             /* channels already hold vx,vy,vz,mass (a BoxField) */
@@ -193,6 +196,24 @@ int vps_set_density_weight(vps_ctx* ctx, double alpha);
  * vps_deposit_fft_z[_slab] (vps_deposit_fft_zy_supported returns 0), and the codes with VPS_FLAG_REFERENCE_MOMENTUM_BUG or
  * VPS_FLAG_INPUT_IS_VM.  VPS_ERR_UNSUPPORTED, before anything is enqueued: a device whose LDS does not hold the 5-channel tile. */
 
+/* Sub-grid stress tensor (an addition within ABI 13: no new symbol; an extension): the second moment itself, of which the three
+ * scalars above are the trace.  S_ij = sum w rho_p v_i v_j, formed per contribution as p_i p_j / rho_p from its [rho v, rho]
+ * record (0 where rho_p = 0), the way S2 is; P, R, vol and w as above.  SIX output channels each, in the order xx, yy, zz, xy,
+ * xz, yz, laid out fields_dev[6][nx][N][N]:
+ *   VPS_SUBGRID_STRESS     vol (S_ij - P_i P_j / R)      tau_ij, the sub-grid (Reynolds) stress of the coarse-grained momentum equation
+ *   VPS_DISPERSION_TENSOR  (S_ij - P_i P_j / R) / R      sigma_ij = tau_ij / (vol R), the velocity-dispersion tensor
+ * all 0 in a cell without mass.  A diagonal channel is clamped at 0 from below; an off-diagonal channel has either sign and is
+ * not clamped.  P_i P_j / R is the float32 expression of the contribution's p_i p_j / rho_p, so a cell with ONE NGP contribution
+ * is exactly 0 in all six channels.  The sum of the three diagonal channels is VPS_SUBGRID_ENERGY (VPS_DISPERSION) up to float32
+ * rounding.
+ * Taken by vps_deposit_field ALONE (NGP and VPS_FLAG_ASSIGN(2 | 3), any x-slab, the workspaces of the 4-channel call).  The one
+ * sort of the call is followed by TWO accumulation launches over the same records, at every N: the diagonal half writes channels
+ * 0..2, the off-diagonal half channels 3..5, each from an LDS tile of the four totals and three second-moment channels (7 cells
+ * floats: 56 KiB, 112 KiB from N = 1024 on).  Both launches are timed under VPS_K_ALGEBRA.
+ * VPS_ERR_ARG with a message naming the quantity, before anything is enqueued: every refusal of the three scalars above, and the
+ * codes with VPS_FLAG_COMPONENTS.  VPS_ERR_UNSUPPORTED, before anything is enqueued: a device whose LDS does not hold the
+ * 7-channel tile. */
+
 /* ---- memory helpers (so the library is usable without torch) ------------ */
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);
 int vps_free(vps_ctx* ctx, void* dev);
@@ -276,7 +297,9 @@ int vps_deposit_ngp(vps_ctx* ctx, const void* pos_dev, int pos_is_f64,
  * VPS_TOTAL_ENERGY, VPS_SUBGRID_ENERGY, VPS_DISPERSION (an addition within ABI 13; "Sub-grid velocity dispersion" above):
  * ncomp = 1, with and without VPS_FLAG_ASSIGN, the same sort records and the same workspaces; the brick's LDS tile carries a
  * fifth channel S2 = sum w rho_p |v_p|^2 (5 cells floats: 40 KiB, 80 KiB from N = 1024 on; VPS_ERR_UNSUPPORTED before anything
- * is enqueued where the context's LDS does not hold it), zeroed and streamed out with the other four. */
+ * is enqueued where the context's LDS does not hold it), zeroed and streamed out with the other four.
+ * VPS_SUBGRID_STRESS, VPS_DISPERSION_TENSOR ("Sub-grid stress tensor" above): ncomp = 6, one sort and two accumulation launches
+ * with a 7-channel tile each. */
 int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const float* vel_dev,
                       const float* rho_dev, int64_t np, int N, double Lbox, int x0, int nx,
                       int quantity, int flags, float* fields_dev, void* work_dev);

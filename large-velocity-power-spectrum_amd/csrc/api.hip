@@ -440,7 +440,8 @@ int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags) {
 }
 
 const char* vps_second_moment_name(int quantity) {
-  static const char* const names[] = {"VPS_TOTAL_ENERGY", "VPS_SUBGRID_ENERGY", "VPS_DISPERSION"};
+  static const char* const names[] = {"VPS_TOTAL_ENERGY", "VPS_SUBGRID_ENERGY", "VPS_DISPERSION", "VPS_SUBGRID_STRESS",
+                                      "VPS_DISPERSION_TENSOR"};
   return vps_quantity_second_moment(quantity) ? names[quantity - VPS_TOTAL_ENERGY] : "";
 }
 

@@ -478,8 +478,47 @@ __device__ __forceinline__ void cell_quantity(float a, float b, float c, float r
   }
 }
 
+// The tensor quantities (VPS_SUBGRID_STRESS, VPS_DISPERSION_TENSOR) are formed by two launches, one per HALF of the six
+// components: the kernels' QUANT is the quantity code for the diagonal half (xx, yy, zz) and the code | TENSOR_OFFDIAG for the
+// off-diagonal half (xy, xz, yz).  The bit exists between vps_deposit_field and its kernels only.
+constexpr int TENSOR_OFFDIAG = 0x100;
+// The contributions rho_p v_i v_j of one [rho v, rho] record to the three second moments of a half, each a correctly rounded
+// division like second_moment_term (exact for integer v and a power of two rho), 0 for a record without mass.  The epilogue
+// forms the resolved part P_i P_j / R with the SAME function of the cell totals.
+template <bool OFFDIAG>
+__device__ __forceinline__ void tensor_terms(float px, float py, float pz, float rho, float m[3]) {
+  if (rho != 0.f) {
+    m[0] = (OFFDIAG ? px * py : px * px) / rho;
+    m[1] = (OFFDIAG ? px * pz : py * py) / rho;
+    m[2] = (OFFDIAG ? py * pz : pz * pz) / rho;
+  } else {
+    m[0] = m[1] = m[2] = 0.f;
+  }
+}
+// One half of a tensor quantity in one cell: d = S_ij - P_i P_j / R from the half's three second moments m0..m2 and the four
+// totals; VPS_SUBGRID_STRESS vol d, VPS_DISPERSION_TENSOR d / R.  A diagonal component is clamped at 0 from below (rounding can
+// take the difference below it), an off-diagonal one has either sign; a cell without mass gives 0.  In a cell with one NGP
+// contribution both sides are the same expression of the same numbers and d is exactly 0.
+template <int QUANT>
+__device__ __forceinline__ void cell_tensor(float a, float b, float c, float rho, float vol, float m0, float m1, float m2,
+                                            float out[4]) {
+  constexpr bool OFFDIAG = (QUANT & TENSOR_OFFDIAG) != 0;
+  static_assert(vps_quantity_tensor(QUANT & ~TENSOR_OFFDIAG), "a tensor quantity code, with or without the half bit");
+  float r[3];
+  tensor_terms<OFFDIAG>(a, b, c, rho, r);
+  const float m[3] = {m0, m1, m2};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float d = m[k] - r[k];
+    const bool keep = rho != 0.f && (OFFDIAG || d > 0.f);
+    if constexpr ((QUANT & ~TENSOR_OFFDIAG) == VPS_SUBGRID_STRESS) out[k] = keep ? vol * d : 0.f;
+    else out[k] = keep ? d / rho : 0.f;
+  }
+  out[3] = 0.f;
+}
+
 // run-time quantity code -> template argument: f(std::integral_constant<int, QUANT>) of the (valid) code.  SECOND_MOMENT: the
-// caller's kernels carry the fifth tile channel (the two deposit kernels of vps_deposit_field); everybody else has no
+// caller's kernels carry the second-moment tile channels (the two deposit kernels of vps_deposit_field); everybody else has no
 // instantiation for those codes and gets VPS_ERR_ARG.
 template <bool SECOND_MOMENT = false, typename Fn>
 int dispatch_quantity(int quantity, Fn&& f) {
@@ -491,6 +530,7 @@ int dispatch_quantity(int quantity, Fn&& f) {
   if constexpr (SECOND_MOMENT) {
     switch (quantity) {
       VPS_Q(VPS_TOTAL_ENERGY); VPS_Q(VPS_SUBGRID_ENERGY); VPS_Q(VPS_DISPERSION);
+      VPS_Q(VPS_SUBGRID_STRESS); VPS_Q(VPS_DISPERSION_TENSOR);
     }
   }
 #undef VPS_Q
@@ -498,11 +538,12 @@ int dispatch_quantity(int quantity, Fn&& f) {
 }
 
 // LDS tile of a deposit kernel that forms `quantity` from C record channels over `cells` cells: one more channel for the
-// second moment (80 KiB where the 4-channel tile has 64: the launch raises the kernel's limit first).
+// second moment (80 KiB where the 4-channel tile has 64: the launch raises the kernel's limit first), three more for one half of
+// a tensor quantity (56 KiB, 112 KiB from N = 1024 on).
 size_t tile_bytes(int C, int cells, int quantity) {
-  return (size_t)(C + (vps_quantity_second_moment(quantity) ? 1 : 0)) * cells * sizeof(float);
+  return (size_t)(C + vps_quantity_moment_channels(quantity)) * cells * sizeof(float);
 }
-// ... and a context whose LDS does not hold the 5-channel tile refuses the quantity
+// ... and a context whose LDS does not hold the 5-channel (7-channel) tile refuses the quantity
 int check_second_moment_tile(vps_ctx* ctx, int quantity, size_t lds) {
   if (vps_quantity_second_moment(quantity) && lds > ctx->lds_per_cu)
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_field: quantity %d (%s) needs an LDS tile of %zu bytes, the device has %zu per CU",
@@ -513,11 +554,17 @@ int check_second_moment_tile(vps_ctx* ctx, int quantity, size_t lds) {
 // ---- the stream-out of an LDS tile [CT][cells], shared by the brick kernels of every route -------------------------------------
 // What the kernel's epilogue is made of, at compile time: C record channels, CT tile channels (the second-moment quantities keep
 // S2 = sum w rho_p |v_p|^2 in a channel of its own behind the C record channels: the records stay [rho v, rho]), NOUT written.
+// A tensor quantity's launch keeps the three second moments of its half (QUANT's TENSOR_OFFDIAG bit) there and writes three.
 template <int C, int EPI, int QUANT>
 struct TileOut {
-  static constexpr bool M2 = EPI == EPI_ALGEBRA && vps_quantity_second_moment(QUANT);
-  static constexpr int CT = M2 ? C + 1 : C;
-  static constexpr int NOUT = (EPI == EPI_RAW) ? C : vps_quantity_channels(QUANT);
+  static constexpr int CODE = QUANT & ~TENSOR_OFFDIAG;
+  static constexpr bool M2 = EPI == EPI_ALGEBRA && vps_quantity_second_moment(CODE);
+  static constexpr bool TENSOR = EPI == EPI_ALGEBRA && vps_quantity_tensor(CODE);
+  static constexpr bool OFFDIAG = TENSOR && (QUANT & TENSOR_OFFDIAG) != 0;
+  static constexpr int CT = M2 ? C + vps_quantity_moment_channels(CODE) : C;
+  static constexpr int NOUT = (EPI == EPI_RAW) ? C : TENSOR ? 3 : vps_quantity_channels(CODE);
+  // what the direct gather adds behind the C record channels: nothing, the trace, a tensor half (assign_gather)
+  static constexpr int MOMENT = TENSOR ? (OFFDIAG ? 3 : 2) : M2 ? 1 : 0;
   static_assert(EPI == EPI_RAW || C == 4, "quantities are formed from [rho v, rho] records");
 };
 // (algebra_cell reads the flags at run time, as it always did; the quantities of rho see their constant 0)
@@ -564,12 +611,26 @@ __device__ __forceinline__ void tile_out4(float* tile, int cells, int loc, bool 
       c4 = *t4;
       *t4 = zero4;
     }
+    float4 c5 = zero4, c6 = zero4;           // the second and third moment of a tensor half
+    if constexpr (T::TENSOR) {
+      float4* t5 = reinterpret_cast<float4*>(tile + 5 * cells + loc);
+      float4* t6 = reinterpret_cast<float4*>(tile + 6 * cells + loc);
+      c5 = *t5; c6 = *t6;
+      *t5 = zero4; *t6 = zero4;
+    }
     if (inside) {
       float rx[4], ry[4], rz[4], rw[4];
-      cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
-      cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
-      cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
-      cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
+      if constexpr (T::TENSOR) {
+        cell_tensor<QUANT>(c0.x, c1.x, c2.x, c3.x, cpar.vol, c4.x, c5.x, c6.x, rx);
+        cell_tensor<QUANT>(c0.y, c1.y, c2.y, c3.y, cpar.vol, c4.y, c5.y, c6.y, ry);
+        cell_tensor<QUANT>(c0.z, c1.z, c2.z, c3.z, cpar.vol, c4.z, c5.z, c6.z, rz);
+        cell_tensor<QUANT>(c0.w, c1.w, c2.w, c3.w, cpar.vol, c4.w, c5.w, c6.w, rw);
+      } else {
+        cell_quantity<QUANT>(c0.x, c1.x, c2.x, c3.x, cflags, cpar, rx, c4.x);
+        cell_quantity<QUANT>(c0.y, c1.y, c2.y, c3.y, cflags, cpar, ry, c4.y);
+        cell_quantity<QUANT>(c0.z, c1.z, c2.z, c3.z, cflags, cpar, rz, c4.z);
+        cell_quantity<QUANT>(c0.w, c1.w, c2.w, c3.w, cflags, cpar, rw, c4.w);
+      }
 #pragma unroll
       for (int c = 0; c < T::NOUT; ++c) {
         vf4 q; q.x = rx[c]; q.y = ry[c]; q.z = rz[c]; q.w = rw[c];
@@ -591,7 +652,8 @@ __device__ __forceinline__ void tile_out1(float* tile, int cells, int loc, bool 
     tile[c * cells + loc] = 0.f;
   }
   if (!inside) return;
-  if constexpr (EPI == EPI_ALGEBRA) cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, T::M2 ? v[T::CT - 1] : 0.f);
+  if constexpr (T::TENSOR) cell_tensor<QUANT>(v[0], v[1], v[2], v[3], cpar.vol, v[C], v[C + 1], v[C + 2], r);
+  else if constexpr (EPI == EPI_ALGEBRA) cell_quantity<QUANT>(v[0], v[1], v[2], v[3], cflags, cpar, r, T::M2 ? v[T::CT - 1] : 0.f);
 #pragma unroll
   for (int c = 0; c < T::NOUT; ++c) {
     const float val = EPI == EPI_ALGEBRA ? r[c] : v[c];
@@ -642,7 +704,13 @@ __global__ void __launch_bounds__(256)
       const unsigned loc = rec[0];
 #pragma unroll
       for (int c = 0; c < C; ++c) atomicAdd(&tile[c * cells + loc], __uint_as_float(rec[1 + c]));   // (vps_lds_add: slower here)
-      if constexpr (M2)
+      if constexpr (TileOut<C, EPI, QUANT>::TENSOR) {
+        float m[3];
+        tensor_terms<TileOut<C, EPI, QUANT>::OFFDIAG>(__uint_as_float(rec[1]), __uint_as_float(rec[2]), __uint_as_float(rec[3]),
+                                                      __uint_as_float(rec[4]), m);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) atomicAdd(&tile[(C + k) * cells + loc], m[k]);
+      } else if constexpr (M2)
         atomicAdd(&tile[C * cells + loc], second_moment_term(__uint_as_float(rec[1]), __uint_as_float(rec[2]),
                                                              __uint_as_float(rec[3]), __uint_as_float(rec[4])));
     }
@@ -1095,11 +1163,19 @@ int deposit_run(vps_ctx* ctx, const void* pos_v, const float* payload, const flo
   if (rc) return rc;
   {
     vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
-    auto launch = [&](auto q) -> int {
+    auto launch_one = [&](auto q, float* dst) -> int {
       auto kern = brick_accumulate_kernel<C, EPI, decltype(q)::value>;
       if (int rcl = raise_lds_limit(ctx, kern, lds)) return rcl;
       hipLaunchKernelGGL(kern, dim3(brick_launch_grid(ctx, lds, l.nbricks)), dim3(256), lds, ctx->stream,
-                         records, start, b, l.nbricks, flags, brick_par(ctx, decltype(q)::value, vol), grid);
+                         records, start, b, l.nbricks, flags, brick_par(ctx, decltype(q)::value & ~TENSOR_OFFDIAG, vol), dst);
+      return VPS_OK;
+    };
+    // (a tensor quantity: the diagonal half into channels 0..2, then the off-diagonal half into 3..5, from the same records)
+    auto launch = [&](auto q) -> int {
+      constexpr int Q = decltype(q)::value;
+      if (int rcl = launch_one(q, grid)) return rcl;
+      if constexpr (EPI == EPI_ALGEBRA && vps_quantity_tensor(Q))
+        return launch_one(std::integral_constant<int, Q | TENSOR_OFFDIAG>{}, grid + 3 * (size_t)nx * N * N);
       return VPS_OK;
     };
     if constexpr (EPI == EPI_RAW) {
@@ -1272,9 +1348,10 @@ __host__ __device__ inline int assign_axis_sources(int i, int bw, int N, int ord
 // The owner-computes gather of brick (ix, iy, iz): records {cell-in-brick of c0, payload[C], 6 weight words} of its source buckets
 // -> LDS float adds into tile [CT][cells].  The brick owns the cells of its range (the last brick of an axis may be partial) on
 // the x rows [cx0, cx1): the whole range, or its part inside a slab -- the other rows of the tile are never added to.  CT = C + 1:
-// the second-moment channel, rho_p |v_p|^2 of [rho v, rho] records, behind the C record channels (TileOut).
+// the second-moment channel, rho_p |v_p|^2 of [rho v, rho] records, behind the C record channels (TileOut); CT = C + 3 with
+// MOMENT = 2 / 3: the diagonal / off-diagonal half of rho_p v_i v_j (TileOut::MOMENT).
 // (`b` by reference: by value the kernels lose 1 - 2 % of their instructions and take up to 4 more VGPRs; DESIGN.md has both)
-template <int C, int CT, int ORDER>
+template <int C, int CT, int ORDER, int MOMENT = (CT > C ? 1 : 0)>
 __device__ __forceinline__ void assign_gather(const unsigned* __restrict__ records, const unsigned* __restrict__ start,
                                               const Bricks& b, int ix, int iy, int iz, int cx0, int cx1, float* tile) {
   constexpr int W = C + 7;
@@ -1319,7 +1396,8 @@ __device__ __forceinline__ void assign_gather(const unsigned* __restrict__ recor
 #pragma unroll
           for (int c = 0; c < C; ++c) pay[c] = __uint_as_float(rec[1 + c]);
           // (the particle's rho_p |v_p|^2, once per record: it takes the same weight product as the four channels)
-          if constexpr (CT > C) pay[C] = second_moment_term(pay[0], pay[1], pay[2], pay[3]);
+          if constexpr (MOMENT >= 2) tensor_terms<MOMENT == 3>(pay[0], pay[1], pay[2], pay[3], pay + C);
+          else if constexpr (CT > C) pay[C] = second_moment_term(pay[0], pay[1], pay[2], pay[3]);
           assign_axis_weights<ORDER>(__uint_as_float(rec[1 + C]), __uint_as_float(rec[2 + C]), wx);
           assign_axis_weights<ORDER>(__uint_as_float(rec[3 + C]), __uint_as_float(rec[4 + C]), wy);
           assign_axis_weights<ORDER>(__uint_as_float(rec[5 + C]), __uint_as_float(rec[6 + C]), wz);
@@ -1412,7 +1490,7 @@ __global__ void __launch_bounds__(256)
     brick_index(b, first + t, ix, iy, iz);
     const int gx0 = ix * b.bx, gy0 = iy * b.by, gz0 = iz * b.bz;
     const int cx0 = max(gx0, x0), cx1 = min(min(gx0 + b.bx, N), x0 + nx);
-    assign_gather<C, CT, ORDER>(records, start, b, ix, iy, iz, cx0, cx1, tile);
+    assign_gather<C, CT, ORDER, TileOut<C, EPI_ALGEBRA, QUANT>::MOMENT>(records, start, b, ix, iy, iz, cx0, cx1, tile);
     __syncthreads();
     // stream the owned rows out (rows of bz cells are contiguous in the slab) and zero them for the next brick
     const int loc_lo = (cx0 - gx0) * rowcells, loc_hi = (cx1 - gx0) * rowcells;
@@ -1504,7 +1582,7 @@ int deposit_assign_field_run(vps_ctx* ctx, const void* pos_v, const float* vel, 
   const F* pos = reinterpret_cast<const F*>(pos_v);
   const int xlo = x0 - (ORDER - 1);
   const int span = nx + ORDER - 1 >= N ? 0x7fffffff : nx + ORDER - 1;     // (the whole ring: every particle passes)
-  const size_t lds = tile_bytes(4, b.cells, quantity);       // (five channels for the second-moment quantities)
+  const size_t lds = tile_bytes(4, b.cells, quantity);       // (five channels for the second-moment scalars, seven for a tensor half)
   if (int rcl = check_second_moment_tile(ctx, quantity, lds)) return rcl;      // before anything is enqueued
   {
     vps_launch_timer tm(ctx, VPS_K_DEPOSIT);
@@ -1518,12 +1596,20 @@ int deposit_assign_field_run(vps_ctx* ctx, const void* pos_v, const float* vel, 
     const int ix_lo = x0 / b.bx, ix_hi = (x0 + nx - 1) / b.bx;
     const long long per_x = (long long)b.nby * b.nbz;
     const long long first = ix_lo * per_x, nbricks = (ix_hi - ix_lo + 1) * per_x;
-    const int rcq = dispatch_quantity<true>(quantity, [&](auto q) -> int {
+    auto launch_one = [&](auto q, float* dst) -> int {
       auto kern = assign_field_kernel<ORDER, decltype(q)::value>;
       if (int rcl = raise_lds_limit(ctx, kern, lds)) return rcl;
       hipLaunchKernelGGL(kern, dim3(brick_launch_grid(ctx, lds, nbricks)), dim3(256), lds, ctx->stream,
                          reinterpret_cast<const unsigned*>(work + p.l.records), reinterpret_cast<const unsigned*>(work + p.l.start),
-                         b, first, nbricks, x0, nx, flags, brick_par(ctx, decltype(q)::value, vol), fields);
+                         b, first, nbricks, x0, nx, flags, brick_par(ctx, decltype(q)::value & ~TENSOR_OFFDIAG, vol), dst);
+      return VPS_OK;
+    };
+    // (a tensor quantity: two gathers over the one sort's records, deposit_run)
+    const int rcq = dispatch_quantity<true>(quantity, [&](auto q) -> int {
+      constexpr int Q = decltype(q)::value;
+      if (int rcl = launch_one(q, fields)) return rcl;
+      if constexpr (vps_quantity_tensor(Q))
+        return launch_one(std::integral_constant<int, Q | TENSOR_OFFDIAG>{}, fields + 3 * (size_t)nx * N * N);
       return VPS_OK;
     });
     if (rcq) return rcq == VPS_ERR_HIP ? rcq : vps_fail(ctx, rcq, "vps_deposit_field: quantity %d", quantity);
@@ -1603,6 +1689,9 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
   if (vps_quantity_second_moment(quantity) && (flags & (VPS_FLAG_REFERENCE_MOMENTUM_BUG | VPS_FLAG_INPUT_IS_VM)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d (%s) takes neither VPS_FLAG_REFERENCE_MOMENTUM_BUG nor VPS_FLAG_INPUT_IS_VM",
+                    quantity, vps_second_moment_name(quantity));
+  if (vps_quantity_tensor(quantity) && (flags & VPS_FLAG_COMPONENT_MASK))
+    return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d (%s) does not take VPS_FLAG_COMPONENTS: its six fields come from two launches",
                     quantity, vps_second_moment_name(quantity));
   if (flags & VPS_FLAG_INPUT_IS_VM) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: VPS_FLAG_INPUT_IS_VM is meaningless here");
   if (!fields_dev || !work_dev || (np > 0 && (!pos_dev || !vel_dev || !rho_dev)))

@@ -6,16 +6,23 @@
 #pragma once
 #include "../../include/vps_hip.h"
 
-constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_DISPERSION; }
+constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_DISPERSION_TENSOR; }
 // one output field, made from rho alone (channel 3 of [rho v, rho])
 constexpr bool vps_quantity_scalar_rho(int q) { return q == VPS_DENSITY || q == VPS_LOG_DENSITY; }
 // one output field that needs the second moment S2 = sum w rho_p |v_p|^2 next to the four cell totals: a fifth tile channel in
 // the deposit kernels (vps_deposit_field), nothing a 4-channel grid, one nearest particle or the pencil kernel can give -- every
 // other entry point refuses these codes (vps_refuse_second_moment)
-constexpr bool vps_quantity_second_moment(int q) { return q >= VPS_TOTAL_ENERGY && q <= VPS_DISPERSION; }
+constexpr bool vps_quantity_second_moment(int q) { return q >= VPS_TOTAL_ENERGY && q <= VPS_DISPERSION_TENSOR; }
+// ... of which the two TENSOR quantities keep the six sums S_ij = sum w rho_p v_i v_j instead of their trace: six output fields
+// (xx, yy, zz, xy, xz, yz), formed by TWO accumulation launches over the one sort's records -- the diagonal half and the
+// off-diagonal half, each with three second-moment tile channels behind the four totals and three output fields
+constexpr bool vps_quantity_tensor(int q) { return q == VPS_SUBGRID_STRESS || q == VPS_DISPERSION_TENSOR; }
 constexpr int vps_quantity_channels(int q) {
-  return q == VPS_VM ? 4 : (q == VPS_ENERGY || vps_quantity_scalar_rho(q) || vps_quantity_second_moment(q)) ? 1 : 3;
+  return q == VPS_VM ? 4 : vps_quantity_tensor(q) ? 6 :
+         (q == VPS_ENERGY || vps_quantity_scalar_rho(q) || vps_quantity_second_moment(q)) ? 1 : 3;
 }
+// second-moment channels of ONE launch's LDS tile: the trace, or one half of the tensor
+constexpr int vps_quantity_moment_channels(int q) { return vps_quantity_tensor(q) ? 3 : vps_quantity_second_moment(q) ? 1 : 0; }
 // reads the context's alpha: VPS_ERR_ARG where it was never set (api.hip: vps_check_weighted)
 constexpr bool vps_quantity_needs_alpha(int q) { return q == VPS_WEIGHTED_VELOCITY || q == VPS_DENSITY; }
 

@@ -31,7 +31,8 @@ MAXNBOX = 500
 LTOT = 1
 remove_bulk_velocity = True
 GRIDDINGS = ("nn", "ngp", "cic", "tsc")
-SECOND_MOMENT = ("total_energy", "subgrid_energy", "dispersion")      # vpower.device.SECOND_MOMENT_QUANTITIES: deposits only
+SECOND_MOMENT = ("total_energy", "subgrid_energy", "dispersion",      # vpower.device.SECOND_MOMENT_QUANTITIES: deposits only
+                 "subgrid_stress", "dispersion_tensor")
 
 
 def build_parser():
@@ -50,10 +51,11 @@ def build_parser():
     p.add_argument("--quantity", type=str, default="velocity", metavar="NAME",
                    help="What to take the spectrum of: velocity (default: the reference's raw nearest-neighbour velocity, Pk.txt "
                         "unchanged), momentum, energy, weighted_velocity, rho13_velocity, rho12_velocity, density, log_density, "
-                        "total_energy, subgrid_energy, dispersion (vpower.device.resolve_quantity; the last three are the "
-                        "kinetic energy of a cell's particles, its part the gridded mean velocity does not resolve, and the velocity "
-                        "dispersion: --gridding ngp, cic or tsc only).  Every quantity but velocity needs PartType0/Density in the "
-                        "snapshot.")
+                        "total_energy, subgrid_energy, dispersion, subgrid_stress, dispersion_tensor (vpower.device.resolve_quantity; "
+                        "the last five are the kinetic energy of a cell's particles, its part the gridded mean velocity does not "
+                        "resolve, the velocity dispersion, and the full contraction of the sub-grid stress tensor and of the "
+                        "velocity-dispersion tensor: --gridding ngp, cic or tsc only).  Every quantity but velocity needs "
+                        "PartType0/Density in the snapshot.")
     p.add_argument("--density-weight", type=float, default=None, metavar="ALPHA",
                    help="Exponent alpha of --quantity weighted_velocity (rho^alpha v) or density (rho^alpha; default 1).")
     p.add_argument("--gridding", type=str, default="nn", choices=GRIDDINGS,
@@ -180,8 +182,11 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
     if gridding != "nn" and density is None:
         raise Exception("every deposit gridding needs the particle densities (the velocity is sum rho v / sum rho)")
     if gridding == "nn" and quantity is not None and device.needs_second_moment(quantity):
-        raise ValueError("the second-moment quantities (total_energy, subgrid_energy, dispersion) need a mass-assignment gridding "
+        raise ValueError("the second-moment quantities (%s) need a mass-assignment gridding " % ", ".join(SECOND_MOMENT) +
                          "(ngp, cic, tsc): one nearest particle has no dispersion")
+    if helmholtz and quantity is not None and device.is_tensor(quantity):
+        raise ValueError("the Helmholtz decomposition takes the three components of a vector quantity, not the six fields of "
+                         "subgrid_stress / dispersion_tensor (quantity %d)" % int(quantity))
     k = kernels if kernels is not None else device.default_kernels()
     pipe = device.PowerPipeline(ntot, ltot, kernels=k, comm=comm, flavour="script", deconvolve=gridding if deconvolve else None)
     lcell = ltot / ntot
@@ -206,7 +211,9 @@ def velocity_spectrum(coords, mass, velocity, ntot, ltot, comm=None, kernels=Non
     if helmholtz:
         tabs = pipe.finish_helmholtz(*pipe.accumulate_helmholtz([grid[0], grid[1], grid[2]]))
         return tuple(_script_table(t) for t in tabs)
-    psum, ns = pipe.accumulate([grid[i] for i in range(grid.shape[0])])
+    # (a tensor quantity's six fields: two groups of three, the off-diagonal group scaled by sqrt(2) -- the full contraction)
+    psum, ns = pipe.accumulate(device.contraction_fields([grid[i] for i in range(grid.shape[0])],
+                                                         quantity if quantity is not None else device.VELOCITY))
     return _script_table(pipe.finish(psum, ns))
 
 

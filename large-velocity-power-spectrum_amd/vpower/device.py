@@ -32,7 +32,12 @@ VELOCITY, MOMENTUM, ENERGY, VM, WEIGHTED, DENSITY, LOG_DENSITY = 0, 1, 2, 3, 4, 
 # the second-moment scalars of a cell's contributions (vps_deposit_field alone forms them: NGP / CIC / TSC deposits), with
 # S2 = sum w rho_p |v_p|^2, P = sum w rho v, R = sum w rho: vol S2, vol (S2 - |P|^2 / R), (S2 - |P|^2 / R) / R
 TOTAL_ENERGY, SUBGRID_ENERGY, DISPERSION = 7, 8, 9
-SECOND_MOMENT_QUANTITIES = {"total_energy": TOTAL_ENERGY, "subgrid_energy": SUBGRID_ENERGY, "dispersion": DISPERSION}
+# ... and the second moment itself, S_ij = sum w rho_p v_i v_j, as six fields xx, yy, zz, xy, xz, yz: the sub-grid stress
+# vol (S_ij - P_i P_j / R) and the velocity-dispersion tensor (S_ij - P_i P_j / R) / R
+SUBGRID_STRESS, DISPERSION_TENSOR = 10, 11
+TENSOR_QUANTITIES = {"subgrid_stress": SUBGRID_STRESS, "dispersion_tensor": DISPERSION_TENSOR}
+SECOND_MOMENT_QUANTITIES = {"total_energy": TOTAL_ENERGY, "subgrid_energy": SUBGRID_ENERGY, "dispersion": DISPERSION,
+                            **TENSOR_QUANTITIES}
 QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED,
             "density": DENSITY, "log_density": LOG_DENSITY, **SECOND_MOMENT_QUANTITIES}
 FLAG_REFERENCE_MOMENTUM_BUG = 1
@@ -40,13 +45,34 @@ FLAG_INPUT_IS_VM = 2
 FLAG_REUSE_SORT = 4
 FLAG_SHARE_ENERGY = 8
 NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3, DENSITY: 1, LOG_DENSITY: 1,      # output channels of a quantity
-         TOTAL_ENERGY: 1, SUBGRID_ENERGY: 1, DISPERSION: 1}                                        # (csrc/quantity.h: vps_quantity_channels)
-SCALAR_QUANTITIES = ("energy", "density", "log_density") + tuple(SECOND_MOMENT_QUANTITIES)      # one field each: dealt out and transformed as one unit
+         TOTAL_ENERGY: 1, SUBGRID_ENERGY: 1, DISPERSION: 1,                                        # (csrc/quantity.h: vps_quantity_channels)
+         SUBGRID_STRESS: 6, DISPERSION_TENSOR: 6}
+SCALAR_QUANTITIES = ("energy", "density", "log_density", "total_energy", "subgrid_energy", "dispersion")      # one field each: dealt out and transformed as one unit
 
 
 def needs_second_moment(quantity):
-    """Whether a quantity (name or code) is one of the second-moment scalars, which only a particle deposit can form."""
+    """Whether a quantity (name or code) is one of the second-moment quantities (the three scalars, the two tensors), which
+    only a particle deposit can form."""
     return quantity in SECOND_MOMENT_QUANTITIES if isinstance(quantity, str) else int(quantity) in SECOND_MOMENT_QUANTITIES.values()
+
+
+def is_tensor(quantity):
+    """Whether a quantity (name or code) is one of the six-field tensor quantities, 'subgrid_stress' / 'dispersion_tensor'."""
+    return quantity in TENSOR_QUANTITIES if isinstance(quantity, str) else int(quantity) in TENSOR_QUANTITIES.values()
+
+
+def contraction_fields(fields, quantity):
+    """The fields whose summed |F|^2 is the spectrum of `quantity`, from the fields a deposit returned.  A tensor quantity's six
+    fields (xx, yy, zz, xy, xz, yz) stand for the nine components of a symmetric tensor: the full contraction
+    sum_ij |T_ij|^2 counts each off-diagonal field twice, so those three are replaced by COPIES scaled by sqrt(2) (float32: the
+    factor's square is 2 to 3e-8; the caller's fields are left as they are) and all six then go through the component-summing
+    passes, three at a time, like any list of fields.  Every other quantity: the list as it is."""
+    fields = list(fields)
+    if is_tensor(quantity):
+        if len(fields) != 6:
+            raise Exception("a tensor quantity has six fields (xx, yy, zz, xy, xz, yz), got %d" % len(fields))
+        fields[3:] = [f * float(np.float32(np.sqrt(2.0))) for f in fields[3:]]
+    return fields
 
 
 class WeightedVelocity(int):
@@ -112,7 +138,7 @@ VECTOR_QUANTITIES = ("velocity", "momentum", "weighted_velocity") + tuple(WEIGHT
 
 def resolve_quantity(quantity, density_weight=None, supported=None):
     """(name, code) of a quantity name of BoxField.spctrm: name is 'velocity' | 'momentum' | 'energy' | 'weighted_velocity' |
-    'density' | 'log_density' | 'total_energy' | 'subgrid_energy' | 'dispersion', code the library's (a WeightedVelocity /
+    'density' | 'log_density' | 'total_energy' | 'subgrid_energy' | 'dispersion' | 'subgrid_stress' | 'dispersion_tensor', code the library's (a WeightedVelocity /
     Density carrying alpha for those two).
     'weighted_velocity' needs density_weight = alpha (finite); 'rho13_velocity' / 'rho12_velocity' are alpha = 1/3 and 1/2;
     'density' is rho^alpha with density_weight = alpha, the plain density (alpha = 1) without; density_weight with any other
@@ -459,7 +485,9 @@ class HipKernels:
         fields of the CIC / TSC cell totals on the slab (VPS_FLAG_ASSIGN: one sort record per particle, the quantity formed in
         the owner brick's epilogue), from a workspace of its own sized by vps_deposit_assign_workspace_bytes.
         TOTAL_ENERGY / SUBGRID_ENERGY / DISPERSION -> [1, nx, N, N]: the scalars of the cell's second moment
-        sum w rho_p |v_p|^2 (a fifth channel of the brick's LDS tile; the same records and workspaces), with every assignment."""
+        sum w rho_p |v_p|^2 (a fifth channel of the brick's LDS tile; the same records and workspaces), with every assignment.
+        SUBGRID_STRESS / DISPERSION_TENSOR -> [6, nx, N, N]: the components xx, yy, zz, xy, xz, yz of that second moment as a
+        tensor (one sort, two accumulation launches with three second-moment tile channels each; the same workspaces)."""
         assign = FLAG_ASSIGN(assignment)
         if int(flags) & FLAG_ASSIGN_MASK:
             # (the workspace below is sized from `assignment`: bits arriving in `flags` would run CIC / TSC in the NGP workspace)

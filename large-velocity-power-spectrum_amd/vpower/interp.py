@@ -394,7 +394,7 @@ class BoxField:
         raise Exception("""Unrecognized physical quantity name.
         Supported: 'velocity', 'momentum', 'energy', 'weighted_velocity' (with density_weight=alpha), 'rho13_velocity',
         'rho12_velocity', 'density' (density_weight=alpha optional), 'log_density'; on particle-backed fields also 'total_energy',
-        'subgrid_energy', 'dispersion'.""")
+        'subgrid_energy', 'dispersion', 'subgrid_stress', 'dispersion_tensor'.""")
 
     def _assigned_fields(self, k, src, quantity, qcode):
         """The fields of a quantity of a lazy particle-backed field (CIC / TSC; NGP for the second-moment quantities): one fused
@@ -442,6 +442,26 @@ class BoxField:
         """(N,N,N) float64 real-space grid of sigma^2 = <|v|^2> - |<v>|^2, the density-weighted velocity dispersion of the
         cell's contributions, >= 0 and 0 in empty cells.  Particle-backed fields only (extension)."""
         return self._second_moment_grid("dispersion")
+
+    def _tensor_grid(self, quantity):
+        src = self._second_moment_source(quantity)
+        f = _kernels().deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, _dev.QUANTITY[quantity],
+                                     assignment=getattr(self, "assignment", "ngp"))
+        return f.cpu().numpy()
+
+    def subgrid_stress(self) -> np.ndarray:
+        """(6,N,N,N) float32 real-space grids of the sub-grid (Reynolds) stress tau_ij = Lcell^3 (S_ij - P_i P_j / R), in the
+        order xx, yy, zz, xy, xz, yz, with S_ij = sum w rho_p v_i v_j, P = sum w rho v and R = sum w rho over the contributions
+        to a cell (weight w of the field's mass assignment).  The diagonals are >= 0, the off-diagonals have either sign; all
+        six are 0 in empty cells and in cells with one NGP particle; the diagonal sum is `subgrid_energy`.  The grids are the
+        kernel's output as it is.  Particle-backed fields only (extension)."""
+        return self._tensor_grid("subgrid_stress")
+
+    def dispersion_tensor(self) -> np.ndarray:
+        """(6,N,N,N) float32 real-space grids of the velocity-dispersion tensor sigma_ij = <v_i v_j> - <v_i><v_j> (density
+        weighted), tau_ij / (Lcell^3 R) of `subgrid_stress`, same order; its trace is `dispersion`.  Particle-backed fields
+        only (extension)."""
+        return self._tensor_grid("dispersion_tensor")
 
     def _power(self, quantity):
         k = _kernels()
@@ -497,7 +517,13 @@ class BoxField:
         energy the gridded mean velocity does not resolve; >= 0) and sigma^2 = <|v|^2> - |<v>|^2; 0 in empty cells.  Only a
         particle-backed field whose grids have not been built can form them (`GasParticles.deposit_to_field(N)`, or with
         assignment='cic' | 'tsc' and method='fused'): one deposit with a fifth LDS tile channel, then the transform of any
-        gridded scalar; every other field raises an Exception naming the quantity.  `deconvolve` as for the other scalars."""
+        gridded scalar; every other field raises an Exception naming the quantity.  `deconvolve` as for the other scalars.
+        'subgrid_stress' and 'dispersion_tensor' (extension): the spectrum of the FULL CONTRACTION sum_ij |T_ij(k)|^2 of the
+        symmetric tensors tau_ij = Lcell^3 (S_ij - P_i P_j / R) and sigma_ij = tau_ij / (Lcell^3 R), S_ij = sum w rho_p v_i v_j:
+        the three diagonal fields once, the three off-diagonal fields twice.  Same fields as the three scalars above, same
+        refusals.  The deposit returns six fields (`subgrid_stress()`); scaled copies (sqrt(2)) of the off-diagonal ones are made on
+        the device and the six go through the component-summing passes three at a time, counted once
+        (`vpower.device.contraction_fields`).  `deconvolve` divides by the assignment's window as for every deposit."""
         quantity, qcode = _dev.resolve_quantity(quantity, density_weight)
         second_moment = _dev.needs_second_moment(qcode)
         if second_moment:
@@ -509,7 +535,7 @@ class BoxField:
         src = getattr(self, "_src", None)
         if src is not None and (second_moment or getattr(self, "assignment", "ngp") != "ngp"):
             # particle-backed CIC / TSC field (deposit_to_field(..., method="fused")): particles -> the fields of this quantity
-            return PowerSpectrum(pipe.spectrum(self._assigned_fields(k, src, quantity, qcode)))
+            return PowerSpectrum(pipe.spectrum(_dev.contraction_fields(self._assigned_fields(k, src, quantity, qcode), qcode)))
         if src is not None and k.fused_supported(self.Nsize, qcode):
             # particle-backed field: particles -> z/y-transformed spectra in one go (no grid in HBM)
             flags = _dev.FLAG_REFERENCE_MOMENTUM_BUG if (quantity == "momentum" and REFERENCE_COMPAT["momentum_bug"]) else 0
@@ -554,6 +580,10 @@ class BoxField:
         solenoidal.  The projection is made in registers by the binning x pass (vps_fft_x_bin_helmholtz): no extra pass
         over the spectrum.  Particle-backed fields go through the fused deposit as `spctrm` does (a second quantity of the
         same field skips the particle sort; momentum leaves the energy field behind for `spctrm('energy')`)."""
+        if isinstance(quantity, str) and _dev.is_tensor(quantity):
+            raise Exception("Unrecognized physical quantity name here: %r is a symmetric tensor of six fields, and the Helmholtz "
+                            "decomposition takes the three components of a vector quantity (%s)"
+                            % (quantity, ", ".join(repr(n) for n in _dev.VECTOR_QUANTITIES)))
         quantity, qcode = _dev.resolve_quantity(quantity, density_weight, supported=_dev.VECTOR_QUANTITIES)
         k = _kernels()
         pipe = _dev.PowerPipeline(self.Nsize, self.Lbox, kernels=k, comm=_dev.SlabComm(enabled=False),
@@ -606,7 +636,8 @@ class BoxField:
         """Two-point correlation function xi(r) = <f(x) . f(x + r)> of a quantity, binned in shells of the lag r (extension; the
         reference has no real-space statistic): the average runs over all N^3 cells x and, per shell, over every lattice lag
         r = Lcell (min(i, N - i), ...) of the periodic box whose length falls into the shell.  Vector quantities give the
-        trace sum_c xi_cc.  Every quantity of `spctrm` is taken, on every kind of field, with the same refusals by name.
+        trace sum_c xi_cc, the tensor quantities the full contraction sum_ij xi_ij,ij.  Every quantity of `spctrm` is taken, on
+        every kind of field, with the same refusals by name.
         Computed through the FFT passes in O(N^3 log N): power grid on the full Hermitian lattice, a second forward transform,
         the exact shell histogram of `spctrm` on the r lattice.  Default shells: edges j Lcell, j = 0 .. N/2 -- the first holds
         r = 0 alone, the last is right-closed at L/2; rmin / rmax / rres give uniform edges rmin + j rres <= rmax instead
@@ -617,7 +648,9 @@ class BoxField:
             self._second_moment_source(quantity)     # (raises by name on a field without particles, before any device work)
         k = _kernels()
         pipe = _dev.CorrelationPipeline(self.Nsize, self.Lbox, kernels=k, rmin=rmin, rmax=rmax, rres=rres)
-        table, xi0 = pipe.correlation(self._real_space_fields(k, quantity, qcode), subtract_mean=subtract_mean)
+        # (a tensor quantity: sum_ij xi_ij,ij, the off-diagonal fields scaled by sqrt(2) as in `spctrm`)
+        fields = _dev.contraction_fields(self._real_space_fields(k, quantity, qcode), qcode)
+        table, xi0 = pipe.correlation(fields, subtract_mean=subtract_mean)
         return CorrelationFunction(table, xi0)
 
     def structure_function(self, quantity="velocity", rmin=None, rmax=None, rres=None, density_weight=None,
