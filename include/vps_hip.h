@@ -86,7 +86,10 @@ enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                     VPS_TOTAL_ENERGY = 7, VPS_SUBGRID_ENERGY = 8, VPS_DISPERSION = 9,
                     /* an addition within ABI 13, vps_deposit_field ONLY: the six components of that second moment as a tensor,
                        see "Sub-grid stress tensor" below */
-                    VPS_SUBGRID_STRESS = 10, VPS_DISPERSION_TENSOR = 11 };
+                    VPS_SUBGRID_STRESS = 10, VPS_DISPERSION_TENSOR = 11,
+                    /* an addition within ABI 13, vps_field_algebra_out ONLY: central differences of the velocity of a whole
+                       gridded field, see "Velocity-gradient fields" below */
+                    VPS_DIVERGENCE = 12, VPS_VORTICITY = 13, VPS_STRAIN_RATE = 14 };
 /* flags for vps_field_algebra */
 #define VPS_FLAG_REFERENCE_MOMENTUM_BUG 1 /* py=pz=vx*mass as interp.py:523-525 */
 #define VPS_FLAG_INPUT_IS_VM 2             /* channels already hold vx,vy,vz,mass (a BoxField) */
@@ -213,6 +216,29 @@ int vps_set_density_weight(vps_ctx* ctx, double alpha);
  * VPS_ERR_ARG with a message naming the quantity, before anything is enqueued: every refusal of the three scalars above, and the
  * codes with VPS_FLAG_COMPONENTS.  VPS_ERR_UNSUPPORTED, before anything is enqueued: a device whose LDS does not hold the
  * 7-channel tile. */
+
+/* Velocity-gradient fields (an addition within ABI 13: no new symbol; an extension): three quantities made of the nine first
+ * derivatives of the velocity u of a WHOLE periodic grid, by second-order central differences.  With h = (float)(1 / (2 Lcell))
+ * rounded once on the host, e_a the unit step along axis a and every index wrapped mod N,
+ *   d_a u_c (i) = (u_c(i + e_a) - u_c(i - e_a)) * h
+ *   VPS_DIVERGENCE   1 channel   (dx ux + dy uy) + dz uz                          the dilatation
+ *   VPS_VORTICITY    3 channels  x: dy uz - dz uy, y: dz ux - dx uz, z: dx uy - dy ux
+ *   VPS_STRAIN_RATE  6 channels  xx, yy, zz, xy, xz, yz (the order of the stress tensor): S_aa = d_a u_a,
+ *                                S_xy = 0.5f * (dy ux + dx uy), S_xz = 0.5f * (dz ux + dx uz), S_yz = 0.5f * (dz uy + dy uz)
+ * in float32 in exactly this order of operations, no fused multiply-add: exact for integer velocities and a power-of-two Lcell.
+ * The transfer function of the scheme is sin(k Lcell) / Lcell for the wavenumber k: the derivative of the field as resolved at
+ * the cell, which is the filter scale of everything the sub-grid quantities above mean -- no higher order is offered.
+ * -tau_ij S_ij of VPS_SUBGRID_STRESS and VPS_STRAIN_RATE is the sub-grid energy flux.
+ * Taken by vps_field_algebra_out ALONE: chans_dev [4][ncell] holds [v, mass] (VPS_FLAG_INPUT_IS_VM is required and is the only
+ * flag taken; channel 3 is not read), out_dev [1 | 3 | 6][ncell] is required and must not overlap chans_dev, and
+ * ncell = N^3 for an integer N >= 4 (with the call's ncell % 4 == 0: N even), the cell (ix, iy, iz) at (ix N + iy) N + iz.  N is
+ * not tied to the FFT sizes.  Whole grids only: an x-slab would need its neighbours' boundary planes.  One launch on the
+ * context's stream, timed under VPS_K_ALGEBRA; every output element has one writer and no atomics are used.
+ * VPS_ERR_ARG with a message naming the quantity, before anything is enqueued: the in-place vps_field_algebra or a null
+ * out_dev; a null chans_dev; overlapping buffers; chans_dev or out_dev not 16-byte aligned; an Lcell that is not positive and
+ * finite, or whose h is not a positive finite float32; a call without VPS_FLAG_INPUT_IS_VM or with any other flag; an ncell that is
+ * no cube, or N < 4; and the three codes on vps_deposit_field, vps_deposit_fft_zy, vps_deposit_fft_z[_slab] (vps_deposit_fft_zy_supported
+ * returns 0) and vps_nn_resample_quantity. */
 
 /* ---- memory helpers (so the library is usable without torch) ------------ */
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);
@@ -438,7 +464,9 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
 int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell,
                       float* chans_dev, int64_t ncell);
 /* Out-of-place form: chans_dev is only read, the result's channels (3: velocity / momentum, 1: energy,
- * 4: VM) go to out_dev[c][ncell]; out_dev == NULL is the in-place call above. */
+ * 4: VM) go to out_dev[c][ncell]; out_dev == NULL is the in-place call above.
+ * VPS_DIVERGENCE / VPS_VORTICITY / VPS_STRAIN_RATE ("Velocity-gradient fields" above): this form only, ncell = N^3 a whole grid
+ * of [v, mass] channels, 1 / 3 / 6 output channels. */
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,
                           int64_t ncell, float* out_dev);
 

@@ -450,3 +450,14 @@ int vps_refuse_second_moment(vps_ctx* ctx, const char* who, int quantity, const 
   return vps_fail(ctx, VPS_ERR_ARG, "%s: quantity %d (%s) is formed by vps_deposit_field only: %s", who, quantity,
                   vps_second_moment_name(quantity), why);
 }
+
+const char* vps_gradient_name(int quantity) {
+  static const char* const names[] = {"VPS_DIVERGENCE", "VPS_VORTICITY", "VPS_STRAIN_RATE"};
+  return vps_quantity_gradient(quantity) ? names[quantity - VPS_DIVERGENCE] : "";
+}
+
+int vps_refuse_gradient(vps_ctx* ctx, const char* who, int quantity, const char* why) {
+  if (!vps_quantity_gradient(quantity)) return VPS_OK;
+  return vps_fail(ctx, VPS_ERR_ARG, "%s: quantity %d (%s) is formed by vps_field_algebra_out only: %s", who, quantity,
+                  vps_gradient_name(quantity), why);
+}

@@ -1686,6 +1686,7 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   int rc = check_deposit_args(ctx, "vps_deposit_field", np, N, Lbox, x0, nx);
   if (rc) return rc;
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
+  if ((rc = vps_refuse_gradient(ctx, "vps_deposit_field", quantity, "a brick's epilogue does not see the neighbouring cells"))) return rc;
   if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
   if (vps_quantity_second_moment(quantity) && (flags & (VPS_FLAG_REFERENCE_MOMENTUM_BUG | VPS_FLAG_INPUT_IS_VM)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d (%s) takes neither VPS_FLAG_REFERENCE_MOMENTUM_BUG nor VPS_FLAG_INPUT_IS_VM",
@@ -1715,8 +1716,9 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
 int vps_deposit_fft_zy_supported(vps_ctx* ctx, int N, int quantity) {
   if (!ctx) return 0;
   // (VPS_VM is four fields of two kinds: not a pencil launch; the second-moment quantities need a fifth tile channel, which the
-  //  pencil kernel does not have)
-  return vps_quantity_valid(quantity) && quantity != VPS_VM && !vps_quantity_second_moment(quantity) && vps_pencil_supported(ctx, N) ? 1 : 0;
+  //  pencil kernel does not have; the gradient quantities need a cell's neighbours in x and y, which a pencil does not hold)
+  return vps_quantity_valid(quantity) && quantity != VPS_VM && !vps_quantity_second_moment(quantity) &&
+         !vps_quantity_gradient(quantity) && vps_pencil_supported(ctx, N) ? 1 : 0;
 }
 
 size_t vps_deposit_fft_zy_workspace_bytes(int64_t np, int N, int nx) {
@@ -1876,6 +1878,7 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   if (rc) return rc;
   if ((rc = refuse_assign_flags(ctx, "vps_deposit_fft_zy", flags))) return rc;
   if ((rc = vps_refuse_second_moment(ctx, "vps_deposit_fft_zy", quantity, "the pencil kernel has no fifth channel"))) return rc;
+  if ((rc = vps_refuse_gradient(ctx, "vps_deposit_fft_zy", quantity, "a pencil does not hold a cell's neighbours in x and y"))) return rc;
   if (!vps_deposit_fft_zy_supported(ctx, N, quantity))
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_fft_zy: N=%d quantity=%d not supported by the fused path", N, quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_fft_zy", quantity, flags))) return rc;
@@ -2002,10 +2005,41 @@ int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell, float
   return vps_field_algebra_out(ctx, quantity, flags, Lcell, chans_dev, ncell, nullptr);
 }
 
+// The velocity-gradient codes of vps_field_algebra_out (include/vps_hip.h, "Velocity-gradient fields"): every refusal names the
+// quantity and comes before anything is enqueued; then one stencil launch (gradient.hip).
+static int field_gradient(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev, int64_t ncell,
+                          float* out_dev) {
+  const char* name = vps_gradient_name(quantity);
+#define VPS_GRAD_FAIL(fmt, ...) vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d (%s) " fmt, quantity, name, ##__VA_ARGS__)
+  if (!out_dev) return VPS_GRAD_FAIL("has no in-place form: it reads a cell's neighbours, out_dev is required (vps_field_algebra_out)");
+  if (flags != VPS_FLAG_INPUT_IS_VM)
+    return VPS_GRAD_FAIL("takes the [v, mass] channels of a gridded field: VPS_FLAG_INPUT_IS_VM and no other flag (flags 0x%x)", flags);
+  const float h = (float)(1.0 / (2.0 * Lcell));
+  if (!(Lcell > 0) || !(h > 0.f) || !std::isfinite(h))
+    return VPS_GRAD_FAIL("needs a positive, finite Lcell whose h = (float)(1 / (2 Lcell)) is positive and finite too");
+  if (!chans_dev) return VPS_GRAD_FAIL("null buffer");
+  // N: the integer cube root, checked exactly (cbrt is within an ulp: N^3 < 2^63 for every candidate)
+  int64_t N = ncell > 0 ? (int64_t)std::llround(std::cbrt((double)ncell)) : 0;
+  if (ncell <= 0 || (ncell & 3) || N < 4 || N > 32768 || N * N * N != ncell)
+    return VPS_GRAD_FAIL("needs a whole periodic grid: ncell = N^3 for an integer N >= 4 and a multiple of 4 (ncell %lld)", (long long)ncell);
+  if (((uintptr_t)chans_dev | (uintptr_t)out_dev) & 15) return VPS_GRAD_FAIL("needs 16-byte aligned buffers");
+  const uintptr_t c0 = (uintptr_t)chans_dev, c1 = c0 + 4 * (uintptr_t)ncell * sizeof(float);
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)vps_quantity_channels(quantity) * (uintptr_t)ncell * sizeof(float);
+  if (o0 < c1 && c0 < o1) return VPS_GRAD_FAIL("out_dev overlaps chans_dev: the stencil reads what a neighbour's store would change");
+#undef VPS_GRAD_FAIL
+  {
+    vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
+    vps_gradient_launch(ctx, quantity, (int)N, h, chans_dev, out_dev);
+  }
+  VPS_HIP_CHECK(ctx, hipGetLastError());
+  return VPS_OK;
+}
+
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,
                           int64_t ncell, float* out_dev) {
   VPS_ENTER(ctx);
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (vps_quantity_gradient(quantity)) return field_gradient(ctx, quantity, flags, Lcell, chans_dev, ncell, out_dev);
   if (int rc = vps_refuse_second_moment(ctx, "vps_field_algebra", quantity, "a 4-channel grid does not hold a second moment")) return rc;
   if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;
   if (int rc = refuse_assign_flags(ctx, "vps_field_algebra", flags)) return rc;

@@ -2,11 +2,12 @@
 // exponent of vps_set_density_weight -- and the two functions of rho that the density-weighted velocity and the scalar density
 // quantities are made of.  Shared by the brick / grid epilogues (deposit.hip), the NN emit (nn.hip) and the pencil kernel
 // (fft_pencil.h).  A new quantity starts here: its code in these five helpers, then its per-cell body in deposit.hip's cell_quantity.
+// (The velocity-gradient codes are no per-cell algebra: a stencil over a whole grid, gradient.hip -- vps_quantity_gradient.)
 // Not part of the ABI.
 #pragma once
 #include "../../include/vps_hip.h"
 
-constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_DISPERSION_TENSOR; }
+constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_STRAIN_RATE; }
 // one output field, made from rho alone (channel 3 of [rho v, rho])
 constexpr bool vps_quantity_scalar_rho(int q) { return q == VPS_DENSITY || q == VPS_LOG_DENSITY; }
 // one output field that needs the second moment S2 = sum w rho_p |v_p|^2 next to the four cell totals: a fifth tile channel in
@@ -17,8 +18,14 @@ constexpr bool vps_quantity_second_moment(int q) { return q >= VPS_TOTAL_ENERGY 
 // (xx, yy, zz, xy, xz, yz), formed by TWO accumulation launches over the one sort's records -- the diagonal half and the
 // off-diagonal half, each with three second-moment tile channels behind the four totals and three output fields
 constexpr bool vps_quantity_tensor(int q) { return q == VPS_SUBGRID_STRESS || q == VPS_DISPERSION_TENSOR; }
+// fields of central differences of a gridded velocity (divergence: 1 field; vorticity: 3; strain rate: 6, in the tensor order):
+// a cell's value needs its six neighbours, which only a whole periodic grid of [v, mass] channels holds -- formed by
+// vps_field_algebra_out alone (gradient.hip), every other entry point refuses these codes (vps_refuse_gradient); no deposit, NN
+// or pencil kernel is instantiated for them (deposit.hip: dispatch_quantity does not know them)
+constexpr bool vps_quantity_gradient(int q) { return q >= VPS_DIVERGENCE && q <= VPS_STRAIN_RATE; }
 constexpr int vps_quantity_channels(int q) {
-  return q == VPS_VM ? 4 : vps_quantity_tensor(q) ? 6 :
+  return q == VPS_DIVERGENCE ? 1 : q == VPS_VORTICITY ? 3 : q == VPS_STRAIN_RATE ? 6 :
+         q == VPS_VM ? 4 : vps_quantity_tensor(q) ? 6 :
          (q == VPS_ENERGY || vps_quantity_scalar_rho(q) || vps_quantity_second_moment(q)) ? 1 : 3;
 }
 // second-moment channels of ONE launch's LDS tile: the trace, or one half of the tensor

@@ -101,6 +101,13 @@ int vps_check_weighted(vps_ctx* ctx, const char* who, int quantity, int flags);
 // anything is enqueued; VPS_OK for every other code.
 int vps_refuse_second_moment(vps_ctx* ctx, const char* who, int quantity, const char* why);
 const char* vps_second_moment_name(int quantity);
+// The velocity-gradient quantities (VPS_DIVERGENCE, VPS_VORTICITY, VPS_STRAIN_RATE) are formed by vps_field_algebra_out alone,
+// from a whole grid; every other entry point that takes a quantity refuses them the same way.
+int vps_refuse_gradient(vps_ctx* ctx, const char* who, int quantity, const char* why);
+const char* vps_gradient_name(int quantity);
+// gradient.hip: the stencil launch behind vps_field_algebra_out for those codes.  chans: [>= 3][N^3] velocity channels, out:
+// [vps_quantity_channels(quantity)][N^3], h = 1 / (2 Lcell) in float32; the caller has checked everything (N even, >= 4).
+void vps_gradient_launch(vps_ctx* ctx, int quantity, int N, float h, const float* chans, float* out);
 
 // Every entry point of the C ABI runs with the context's device current and restores the caller's
 // on return: the library allocates (tables, partial sums, lattice axes) and launches on streams

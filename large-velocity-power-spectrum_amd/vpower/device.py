@@ -38,6 +38,11 @@ SUBGRID_STRESS, DISPERSION_TENSOR = 10, 11
 TENSOR_QUANTITIES = {"subgrid_stress": SUBGRID_STRESS, "dispersion_tensor": DISPERSION_TENSOR}
 SECOND_MOMENT_QUANTITIES = {"total_energy": TOTAL_ENERGY, "subgrid_energy": SUBGRID_ENERGY, "dispersion": DISPERSION,
                             **TENSOR_QUANTITIES}
+# central differences of the velocity of a WHOLE gridded field (vps_field_algebra_out alone forms them, csrc/gradient.hip):
+# the dilatation, the vorticity (x, y, z) and the strain rate (xx, yy, zz, xy, xz, yz).  Kept OUT of QUANTITY: they are fields
+# (BoxField.divergence / vorticity / strain_rate, HipKernels.velocity_gradient), not names the spectrum routes take.
+DIVERGENCE, VORTICITY, STRAIN_RATE = 12, 13, 14
+GRADIENT_QUANTITIES = {"divergence": DIVERGENCE, "vorticity": VORTICITY, "strain_rate": STRAIN_RATE}
 QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED,
             "density": DENSITY, "log_density": LOG_DENSITY, **SECOND_MOMENT_QUANTITIES}
 FLAG_REFERENCE_MOMENTUM_BUG = 1
@@ -46,7 +51,7 @@ FLAG_REUSE_SORT = 4
 FLAG_SHARE_ENERGY = 8
 NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3, DENSITY: 1, LOG_DENSITY: 1,      # output channels of a quantity
          TOTAL_ENERGY: 1, SUBGRID_ENERGY: 1, DISPERSION: 1,                                        # (csrc/quantity.h: vps_quantity_channels)
-         SUBGRID_STRESS: 6, DISPERSION_TENSOR: 6}
+         SUBGRID_STRESS: 6, DISPERSION_TENSOR: 6, DIVERGENCE: 1, VORTICITY: 3, STRAIN_RATE: 6}
 SCALAR_QUANTITIES = ("energy", "density", "log_density", "total_energy", "subgrid_energy", "dispersion")      # one field each: dealt out and transformed as one unit
 
 
@@ -73,6 +78,21 @@ def contraction_fields(fields, quantity):
             raise Exception("a tensor quantity has six fields (xx, yy, zz, xy, xz, yz), got %d" % len(fields))
         fields[3:] = [f * float(np.float32(np.sqrt(2.0))) for f in fields[3:]]
     return fields
+
+
+def flux_contraction(tau, S):
+    """Pi = -tau_ij S_ij from the six fields (xx, yy, zz, xy, xz, yz) of a symmetric stress tau and of the strain rate S, each
+    [6, ...]: -(tau_xx S_xx + tau_yy S_yy + tau_zz S_zz + 2 tau_xy S_xy + 2 tau_xz S_xz + 2 tau_yz S_yz), elementwise in the
+    tensors' dtype and in this order of additions (the off-diagonal fields stand for two components each)."""
+    if tau.shape != S.shape or tau.shape[0] != 6:
+        raise Exception("the flux contraction takes two tensors of six fields (xx, yy, zz, xy, xz, yz), got %s and %s"
+                        % (tuple(tau.shape), tuple(S.shape)))
+    acc = tau[0] * S[0]
+    acc += tau[1] * S[1]
+    acc += tau[2] * S[2]
+    for c in (3, 4, 5):
+        acc += 2.0 * (tau[c] * S[c])
+    return acc.neg_()
 
 
 class WeightedVelocity(int):
@@ -670,6 +690,29 @@ class HipKernels:
         out = self.empty((nout,) + tuple(chans.shape[1:]), torch.float32)
         self._chk(self.lib.vps_field_algebra_out(self.ctx, quantity, flags, float(Lcell),
                                                  self._ptr(chans, torch.float32), ncell, self._ptr(out)))
+        return out
+
+    def velocity_gradient(self, chans, N, Lcell, what, out=None):
+        """Central-difference fields of the velocity of a whole periodic grid (vps_field_algebra_out, csrc/gradient.hip): chans
+        [4, N, N, N] float32 = vx, vy, vz, mass (the mass is not read), `what` 'divergence' | 'vorticity' | 'strain_rate' or its
+        code -> [1 | 3 | 6, N, N, N] float32 (vorticity x, y, z; strain rate xx, yy, zz, xy, xz, yz), d_a u_c =
+        (u_c(i + e_a) - u_c(i - e_a)) / (2 Lcell) with every index wrapped.  `out`: a tensor of that shape to write into; it must
+        not overlap `chans`."""
+        code = GRADIENT_QUANTITIES.get(what, what) if isinstance(what, str) else int(what)
+        if code not in GRADIENT_QUANTITIES.values():
+            raise ValueError("velocity_gradient forms %s, not %r" % (" | ".join(repr(n) for n in GRADIENT_QUANTITIES), what))
+        N = int(N)
+        if tuple(chans.shape) != (4, N, N, N):
+            raise ValueError("velocity_gradient needs the [4, N, N, N] channels of a whole grid, got %s for N = %d"
+                             % (tuple(chans.shape), N))
+        self._stream()
+        shape = (NCOMP[code], N, N, N)
+        if out is None:
+            out = self.empty(shape, torch.float32)
+        elif tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError("velocity_gradient: out must be a contiguous %s tensor" % (shape,))
+        self._chk(self.lib.vps_field_algebra_out(self.ctx, code, FLAG_INPUT_IS_VM, float(Lcell),
+                                                 self._ptr(chans, torch.float32), N ** 3, self._ptr(out, torch.float32)))
         return out
 
     # -- stage B + C ------------------------------------------------------------

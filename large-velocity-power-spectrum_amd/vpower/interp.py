@@ -327,9 +327,13 @@ class BoxField:
         self._nn_src = None
         src = getattr(self, "_src", None)
         if src is not None and self._chans is None and not self._host:
-            self._chans = _kernels().deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, _dev.VM,
-                                                   assignment=getattr(self, "assignment", "ngp"))
+            self._chans = self._build_vm_chans(_kernels(), src)
         self._src = None
+
+    def _build_vm_chans(self, k, src):
+        """[v, mass] channels of the particles src = (pos, vel, rho), gridded by the field's assignment."""
+        return k.deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, _dev.VM,
+                               assignment=getattr(self, "assignment", "ngp"))
 
     def _get(self, name, ch):
         self._materialise()
@@ -462,6 +466,67 @@ class BoxField:
         weighted), tau_ij / (Lcell^3 R) of `subgrid_stress`, same order; its trace is `dispersion`.  Particle-backed fields
         only (extension)."""
         return self._tensor_grid("dispersion_tensor")
+
+    # -- derivative fields: central differences of the gridded velocity ----------------
+    def _gradient_chans(self, k):
+        """The [v, mass] channels on the device for a derivative field.  A lazy particle-backed field grids them by its own
+        assignment and KEEPS its particles (the second-moment quantities stay available); the channels are the ones `get_v()`
+        would build and are kept, so both see the same numbers."""
+        src = getattr(self, "_src", None)
+        if src is None:
+            return self._device_chans(k)
+        if self._chans is None:                    # (the call of _materialise, which then finds them built)
+            self._chans = self._build_vm_chans(k, src)
+        return self._chans
+
+    def _gradient_grid(self, what):
+        k = _kernels()
+        return k.velocity_gradient(self._gradient_chans(k), self.Nsize, self.Lcell, what)
+
+    def divergence(self) -> np.ndarray:
+        """(N,N,N) float32 real-space grid of the dilatation div u = dx ux + dy uy + dz uz of the gridded velocity, by
+        second-order central differences d_a u_c = (u_c(i + e_a) - u_c(i - e_a)) / (2 Lcell) on the periodic grid (transfer
+        function sin(k Lcell) / Lcell: the derivative at the cell scale, which is the filter scale of the sub-grid quantities).
+        Works on every kind of field: host-built, neighbour-backed, and particle-backed through its gridded [v, mass] channels.
+        EMPTY CELLS of a sparse NGP grid hold u = 0 and make spurious gradients against their neighbours: for derivative fields
+        grid with CIC or TSC (`deposit_to_field(N, assignment='cic' | 'tsc', method='fused')`) or take the neighbour route
+        (`ann_interp_to_field`), which leaves no cell empty.  Whole grids only: there is no halo exchange for x-slabs, and the
+        multi-rank driver script does not form these fields.  The grid is the kernel's output as it is (extension)."""
+        return self._gradient_grid("divergence")[0].cpu().numpy()
+
+    def vorticity(self) -> np.ndarray:
+        """(3,N,N,N) float32 real-space grids of the vorticity curl u of the gridded velocity: x = dy uz - dz uy,
+        y = dz ux - dx uz, z = dx uy - dy ux, by the central differences of `divergence` -- see there for the scheme, for EMPTY
+        CELLS of a sparse NGP grid (u = 0 there: spurious gradients; use CIC / TSC with method='fused', or the neighbour route)
+        and for the restriction to whole grids (no halo exchange for x-slabs; not in the driver script).  Extension."""
+        return self._gradient_grid("vorticity").cpu().numpy()
+
+    def strain_rate(self) -> np.ndarray:
+        """(6,N,N,N) float32 real-space grids of the strain rate S_ij = (d_j u_i + d_i u_j) / 2 of the gridded velocity, in the
+        order xx, yy, zz, xy, xz, yz of `subgrid_stress`; its trace is `divergence`.  Central differences as in `divergence` --
+        see there for the scheme, for EMPTY CELLS of a sparse NGP grid (u = 0 there: spurious gradients; use CIC / TSC with
+        method='fused', or the neighbour route) and for the restriction to whole grids (no halo exchange for x-slabs; not in the
+        driver script).  Extension."""
+        return self._gradient_grid("strain_rate").cpu().numpy()
+
+    def subgrid_flux(self) -> np.ndarray:
+        """(N,N,N) float32 real-space grid of the sub-grid energy flux
+        Pi = -(tau_xx S_xx + tau_yy S_yy + tau_zz S_zz + 2 tau_xy S_xy + 2 tau_xz S_xz + 2 tau_yz S_yz) = -tau_ij S_ij,
+        the energy per time the resolved flow hands to the motions below the cell scale (Pi > 0: forward cascade), at the filter
+        scale l = Lcell: tau is the `subgrid_stress` grid and S the `strain_rate` of the velocity gridded by the same assignment.
+        UNITS: tau carries the cell volume (tau_ij = Lcell^3 (S_ij - P_i P_j / R), a momentum-flux times a volume), so Pi is an
+        energy per time PER CELL, not a density: divide by Lcell^3 for the flux density, and sum (not average) over cells for a
+        region's transfer rate.  The contraction is elementwise float32 on the device, in the order of additions written above.
+        Particle-backed fields only, like `subgrid_stress` (the same refusal by name on the other kinds).  EMPTY CELLS of a
+        sparse NGP grid hold u = 0 and make spurious gradients in S: use CIC or TSC with method='fused'
+        (`deposit_to_field(N, assignment='cic' | 'tsc', method='fused')`).  Whole grids only: no halo exchange for x-slabs, not in
+        the driver script.  Extension."""
+        src = self._second_moment_source("subgrid_flux")
+        k = _kernels()
+        tau = k.deposit_field(src[0], src[1], src[2], self.Nsize, self.Lbox, 0, self.Nsize, _dev.SUBGRID_STRESS,
+                              assignment=getattr(self, "assignment", "ngp"))
+        S = k.velocity_gradient(self._gradient_chans(k), self.Nsize, self.Lcell, "strain_rate")
+        return _dev.flux_contraction(tau, S).cpu().numpy()
 
     def _power(self, quantity):
         k = _kernels()
