@@ -89,7 +89,12 @@ enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                     VPS_SUBGRID_STRESS = 10, VPS_DISPERSION_TENSOR = 11,
                     /* an addition within ABI 13, vps_field_algebra_out ONLY: central differences of the velocity of a whole
                        gridded field, see "Velocity-gradient fields" below */
-                    VPS_DIVERGENCE = 12, VPS_VORTICITY = 13, VPS_STRAIN_RATE = 14 };
+                    VPS_DIVERGENCE = 12, VPS_VORTICITY = 13, VPS_STRAIN_RATE = 14,
+                    /* an addition within ABI 13, vps_field_algebra_out ONLY: the mass-weighted box filter of a whole gridded
+                       field at a chosen half-width, see "Box-filtered fields" below.  The code 15 is left unassigned ON PURPOSE:
+                       it is the code hosts and tests probe as "the first unknown quantity" (VPS_ERR_ARG, "quantity 15") and
+                       stays that */
+                    VPS_FILTERED_VM = 16, VPS_FILTERED_STRESS = 17 };
 /* flags for vps_field_algebra */
 #define VPS_FLAG_REFERENCE_MOMENTUM_BUG 1 /* py=pz=vx*mass as interp.py:523-525 */
 #define VPS_FLAG_INPUT_IS_VM 2             /* channels already hold vx,vy,vz,mass (a BoxField) */
@@ -121,6 +126,9 @@ enum vps_quantity { VPS_VELOCITY = 0, VPS_MOMENTUM = 1, VPS_ENERGY = 2,
                                               vps_deposit_fft_z[_slab], vps_field_algebra[_out], vps_nn_resample_quantity) or together
                                               with VPS_FLAG_INPUT_IS_VM: VPS_ERR_ARG before anything is enqueued. */
 #define VPS_FLAG_ASSIGN_MASK 0x300
+#define VPS_FLAG_FILTER(m) (((m) & 0xfff) << 12)   /* half-width m in cells, box of (2m+1)^3 cells */
+#define VPS_FLAG_FILTER_MASK 0xfff000              /* VPS_FILTERED_VM / VPS_FILTERED_STRESS ONLY (an addition within ABI 13), see
+                                              "Box-filtered fields"; no other code or entry point gives the field a meaning */
 
 /* ---- lifecycle ---------------------------------------------------------- */
 int vps_create(vps_ctx** out, int device_id);
@@ -239,6 +247,40 @@ int vps_set_density_weight(vps_ctx* ctx, double alpha);
  * finite, or whose h is not a positive finite float32; a call without VPS_FLAG_INPUT_IS_VM or with any other flag; an ncell that is
  * no cube, or N < 4; and the three codes on vps_deposit_field, vps_deposit_fft_zy, vps_deposit_fft_z[_slab] (vps_deposit_fft_zy_supported
  * returns 0) and vps_nn_resample_quantity. */
+
+/* Box-filtered fields (an addition within ABI 13: no new symbol; an extension): the gridded field coarse-grained with a periodic
+ * box of (2m+1)^3 cells, half-width m = (flags & VPS_FLAG_FILTER_MASK) >> 12, on the grid it already has -- the filter scale is
+ * l = (2m+1) Lcell.  W(i) is the box centred on cell i, every index wrapped mod N.  Per cell, from chans_dev [4][ncell] =
+ * [u_x, u_y, u_z, mass], in float32 with no fused multiply-add:  p_c = mass * u_c  and  s_ij = p_i * u_j (i <= j).  Box sums
+ * M = sum_W mass, P_c = sum_W p_c, S_ij = sum_W s_ij; c = (float)(1 / (2m+1)^3) rounded once on the host.
+ *   VPS_FILTERED_VM      4 channels  u~_c = P_c / M, mbar = M * c (both 0 where the box holds no mass): again a [v, mass] grid -- the Favre-filtered
+ *                                    velocity and the filtered mass -- which every entry point that takes VPS_FLAG_INPUT_IS_VM
+ *                                    reads (spectra, correlations, the gradient codes above, totals)
+ *   VPS_FILTERED_STRESS  6 channels  xx, yy, zz, xy, xz, yz:  tau_l,ij = (S_ij - (P_i * P_j) / M) * c  in exactly this order of
+ *                                    operations; a diagonal channel is clamped at 0 from below BEFORE the multiplication by c, an
+ *                                    off-diagonal channel is not clamped; all six are 0 where M == 0.  Units of
+ *                                    VPS_SUBGRID_STRESS: mass x velocity^2 per cell.
+ * FIXED: the two products per cell, the division, the subtraction, the clamp and the multiplication by c, each one float32
+ * rounding in the order written.  NOT FIXED: the order of the additions inside a box sum -- the kernel (filter.hip) adds along z
+ * with a sliding sum inside groups of 4 (2 where N % 4 == 2) cells, keeps the x sum as a running sum that adds plane x + m and
+ * removes plane x - m - 1 and restarts from a direct sum every x chunk of at most 64 planes, and adds along y directly: a sum
+ * carries at most K = 6m + 134 roundings (filter.hip derives it).  A rounding of a sliding sum is relative to the window sum it is
+ * made at: with A(i) = sum_W(i) |terms|, |error at (x, y, z)| <= K 2^-24 max A(x', y, z') over x' <= x in the chunk of x and z' <= z
+ * in the group of z -- where the mass falls by many orders of magnitude within a chunk's planes, the sums of the faint region are
+ * only that good.  Whether a box holds mass is decided EXACTLY (a count of the cells with mass != 0 is summed next to M, and
+ * sums of ones are exact): a box without such a cell gives exact zeros in every channel, mbar included.  Sums of
+ * integers below 2^24 are exact in any order.  The transfer function of the filter is prod_a sin((2m+1) k_a Lcell / 2) /
+ * ((2m+1) sin(k_a Lcell / 2)).  tau_l is the stress of the GRIDDED field: on a particle-backed field it does not hold the
+ * dispersion inside a cell, which stays VPS_SUBGRID_STRESS.
+ * Taken by vps_field_algebra_out ALONE: VPS_FLAG_INPUT_IS_VM is required, out_dev [4 | 6][ncell] is required and must not overlap
+ * chans_dev, ncell = N^3 for an even N >= 4, Lcell positive and finite (not otherwise used).  Whole grids only.  The call
+ * allocates nothing: one launch on the context's stream, timed under VPS_K_ALGEBRA; every output element has one writer, no atomics.
+ * VPS_ERR_ARG with a message naming the quantity, before anything is enqueued: the in-place vps_field_algebra or a null out_dev; a
+ * null chans_dev; overlapping buffers; a buffer that is not 16-byte aligned; a call without VPS_FLAG_INPUT_IS_VM; any flag bit
+ * other than VPS_FLAG_INPUT_IS_VM and the filter field; m == 0; 2m+1 > N; an ncell that is not the cube of an even N >= 4; an Lcell
+ * that is not positive and finite; and the two codes on vps_deposit_field, vps_deposit_fft_zy, vps_deposit_fft_z[_slab]
+ * (vps_deposit_fft_zy_supported returns 0) and vps_nn_resample_quantity.  VPS_ERR_UNSUPPORTED, before anything is enqueued: m > 8,
+ * the largest half-width the kernel's LDS plan holds (the message names it); every 1 <= m <= 8 is taken at every even N >= 2m+2. */
 
 /* ---- memory helpers (so the library is usable without torch) ------------ */
 int vps_malloc(vps_ctx* ctx, void** dev, size_t bytes);
@@ -465,6 +507,8 @@ int vps_field_algebra(vps_ctx* ctx, int quantity, int flags, double Lcell,
                       float* chans_dev, int64_t ncell);
 /* Out-of-place form: chans_dev is only read, the result's channels (3: velocity / momentum, 1: energy,
  * 4: VM) go to out_dev[c][ncell]; out_dev == NULL is the in-place call above.
+ * VPS_FILTERED_VM / VPS_FILTERED_STRESS ("Box-filtered fields" above): this form only, ncell = N^3 a whole grid, the half-width
+ * in VPS_FLAG_FILTER(m).
  * VPS_DIVERGENCE / VPS_VORTICITY / VPS_STRAIN_RATE ("Velocity-gradient fields" above): this form only, ncell = N^3 a whole grid
  * of [v, mass] channels, 1 / 3 / 6 output channels. */
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,

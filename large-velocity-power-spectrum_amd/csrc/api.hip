@@ -456,8 +456,12 @@ const char* vps_gradient_name(int quantity) {
   return vps_quantity_gradient(quantity) ? names[quantity - VPS_DIVERGENCE] : "";
 }
 
-int vps_refuse_gradient(vps_ctx* ctx, const char* who, int quantity, const char* why) {
-  if (!vps_quantity_gradient(quantity)) return VPS_OK;
+const char* vps_filter_name(int quantity) {
+  return quantity == VPS_FILTERED_VM ? "VPS_FILTERED_VM" : quantity == VPS_FILTERED_STRESS ? "VPS_FILTERED_STRESS" : "";
+}
+
+int vps_refuse_grid_only(vps_ctx* ctx, const char* who, int quantity, const char* why) {
+  if (!vps_quantity_gradient(quantity) && !vps_quantity_filter(quantity)) return VPS_OK;
   return vps_fail(ctx, VPS_ERR_ARG, "%s: quantity %d (%s) is formed by vps_field_algebra_out only: %s", who, quantity,
-                  vps_gradient_name(quantity), why);
+                  vps_quantity_filter(quantity) ? vps_filter_name(quantity) : vps_gradient_name(quantity), why);
 }

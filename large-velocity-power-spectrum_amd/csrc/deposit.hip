@@ -1686,7 +1686,7 @@ int vps_deposit_field(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, const f
   int rc = check_deposit_args(ctx, "vps_deposit_field", np, N, Lbox, x0, nx);
   if (rc) return rc;
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d", quantity);
-  if ((rc = vps_refuse_gradient(ctx, "vps_deposit_field", quantity, "a brick's epilogue does not see the neighbouring cells"))) return rc;
+  if ((rc = vps_refuse_grid_only(ctx, "vps_deposit_field", quantity, "a brick's epilogue does not see the neighbouring cells"))) return rc;
   if ((rc = vps_check_weighted(ctx, "vps_deposit_field", quantity, flags))) return rc;
   if (vps_quantity_second_moment(quantity) && (flags & (VPS_FLAG_REFERENCE_MOMENTUM_BUG | VPS_FLAG_INPUT_IS_VM)))
     return vps_fail(ctx, VPS_ERR_ARG, "vps_deposit_field: quantity %d (%s) takes neither VPS_FLAG_REFERENCE_MOMENTUM_BUG nor VPS_FLAG_INPUT_IS_VM",
@@ -1718,7 +1718,7 @@ int vps_deposit_fft_zy_supported(vps_ctx* ctx, int N, int quantity) {
   // (VPS_VM is four fields of two kinds: not a pencil launch; the second-moment quantities need a fifth tile channel, which the
   //  pencil kernel does not have; the gradient quantities need a cell's neighbours in x and y, which a pencil does not hold)
   return vps_quantity_valid(quantity) && quantity != VPS_VM && !vps_quantity_second_moment(quantity) &&
-         !vps_quantity_gradient(quantity) && vps_pencil_supported(ctx, N) ? 1 : 0;
+         !vps_quantity_gradient(quantity) && !vps_quantity_filter(quantity) && vps_pencil_supported(ctx, N) ? 1 : 0;
 }
 
 size_t vps_deposit_fft_zy_workspace_bytes(int64_t np, int N, int nx) {
@@ -1878,7 +1878,7 @@ static int deposit_fft_impl(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, c
   if (rc) return rc;
   if ((rc = refuse_assign_flags(ctx, "vps_deposit_fft_zy", flags))) return rc;
   if ((rc = vps_refuse_second_moment(ctx, "vps_deposit_fft_zy", quantity, "the pencil kernel has no fifth channel"))) return rc;
-  if ((rc = vps_refuse_gradient(ctx, "vps_deposit_fft_zy", quantity, "a pencil does not hold a cell's neighbours in x and y"))) return rc;
+  if ((rc = vps_refuse_grid_only(ctx, "vps_deposit_fft_zy", quantity, "a pencil does not hold a cell's neighbours in x and y"))) return rc;
   if (!vps_deposit_fft_zy_supported(ctx, N, quantity))
     return vps_fail(ctx, VPS_ERR_UNSUPPORTED, "vps_deposit_fft_zy: N=%d quantity=%d not supported by the fused path", N, quantity);
   if ((rc = vps_check_weighted(ctx, "vps_deposit_fft_zy", quantity, flags))) return rc;
@@ -2035,10 +2035,45 @@ static int field_gradient(vps_ctx* ctx, int quantity, int flags, double Lcell, c
   return VPS_OK;
 }
 
+// The box-filter codes of vps_field_algebra_out (include/vps_hip.h, "Box-filtered fields"): every refusal names the quantity and
+// comes before anything is enqueued; then one launch (filter.hip).
+static int field_filter(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev, int64_t ncell,
+                        float* out_dev) {
+  const char* name = vps_filter_name(quantity);
+#define VPS_FILT_FAIL(code, fmt, ...) vps_fail(ctx, code, "vps_field_algebra: quantity %d (%s) " fmt, quantity, name, ##__VA_ARGS__)
+  if (!out_dev) return VPS_FILT_FAIL(VPS_ERR_ARG, "has no in-place form: it reads a box of cells, out_dev is required (vps_field_algebra_out)");
+  if (!(flags & VPS_FLAG_INPUT_IS_VM) || (flags & ~(VPS_FLAG_INPUT_IS_VM | VPS_FLAG_FILTER_MASK)))
+    return VPS_FILT_FAIL(VPS_ERR_ARG, "takes the [v, mass] channels of a gridded field: VPS_FLAG_INPUT_IS_VM, VPS_FLAG_FILTER(m) and no other flag (flags 0x%x)", flags);
+  if (!(Lcell > 0) || !std::isfinite(Lcell)) return VPS_FILT_FAIL(VPS_ERR_ARG, "needs a positive, finite Lcell");
+  if (!chans_dev) return VPS_FILT_FAIL(VPS_ERR_ARG, "null buffer");
+  int64_t N = ncell > 0 ? (int64_t)std::llround(std::cbrt((double)ncell)) : 0;
+  if (ncell <= 0 || (N & 1) || N < 4 || N > 32768 || N * N * N != ncell)
+    return VPS_FILT_FAIL(VPS_ERR_ARG, "needs a whole periodic grid: ncell = N^3 for an even N >= 4 (ncell %lld)", (long long)ncell);
+  const int m = (flags & VPS_FLAG_FILTER_MASK) >> 12;
+  if (m < 1) return VPS_FILT_FAIL(VPS_ERR_ARG, "needs a half-width: VPS_FLAG_FILTER(m) with m >= 1 (flags 0x%x)", flags);
+  if (2 * (int64_t)m + 1 > N) return VPS_FILT_FAIL(VPS_ERR_ARG, "the box of 2m + 1 = %d cells is wider than the grid (N = %lld)", 2 * m + 1, (long long)N);
+  if (((uintptr_t)chans_dev | (uintptr_t)out_dev) & 15) return VPS_FILT_FAIL(VPS_ERR_ARG, "needs 16-byte aligned buffers");
+  const uintptr_t c0 = (uintptr_t)chans_dev, c1 = c0 + 4 * (uintptr_t)ncell * sizeof(float);
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)vps_quantity_channels(quantity) * (uintptr_t)ncell * sizeof(float);
+  if (o0 < c1 && c0 < o1) return VPS_FILT_FAIL(VPS_ERR_ARG, "out_dev overlaps chans_dev: a box sum reads what a neighbour's store would change");
+  if (m > VPS_FILTER_MAX_HALF_WIDTH)
+    return VPS_FILT_FAIL(VPS_ERR_UNSUPPORTED, "half-width m = %d: the largest half-width taken is %d (the LDS plan of the kernel)", m, VPS_FILTER_MAX_HALF_WIDTH);
+#undef VPS_FILT_FAIL
+  const double w = 2.0 * m + 1.0;
+  const float c = (float)(1.0 / (w * w * w));
+  {
+    vps_launch_timer tm(ctx, VPS_K_ALGEBRA);
+    vps_filter_launch(ctx, quantity, (int)N, m, c, chans_dev, out_dev);
+  }
+  VPS_HIP_CHECK(ctx, hipGetLastError());
+  return VPS_OK;
+}
+
 int vps_field_algebra_out(vps_ctx* ctx, int quantity, int flags, double Lcell, const float* chans_dev,
                           int64_t ncell, float* out_dev) {
   VPS_ENTER(ctx);
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_field_algebra: quantity %d", quantity);
+  if (vps_quantity_filter(quantity)) return field_filter(ctx, quantity, flags, Lcell, chans_dev, ncell, out_dev);
   if (vps_quantity_gradient(quantity)) return field_gradient(ctx, quantity, flags, Lcell, chans_dev, ncell, out_dev);
   if (int rc = vps_refuse_second_moment(ctx, "vps_field_algebra", quantity, "a 4-channel grid does not hold a second moment")) return rc;
   if (int rc = vps_check_weighted(ctx, "vps_field_algebra", quantity, flags)) return rc;

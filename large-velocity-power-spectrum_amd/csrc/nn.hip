@@ -1967,7 +1967,7 @@ int vps_nn_resample_quantity(vps_ctx* ctx, const void* pos_dev, int pos_is_f64, 
   if (!(Lcell > 0) || !out_dev) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: bad Lcell / null output");
   if (!vps_quantity_valid(quantity)) return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: quantity %d", quantity);
   if (int rc = vps_refuse_second_moment(ctx, "vps_nn_resample_quantity", quantity, "one nearest particle has no dispersion")) return rc;
-  if (int rc = vps_refuse_gradient(ctx, "vps_nn_resample_quantity", quantity, "the emit of a lattice point does not see its neighbours")) return rc;
+  if (int rc = vps_refuse_grid_only(ctx, "vps_nn_resample_quantity", quantity, "the emit of a lattice point does not see its neighbours")) return rc;
   if (flags & VPS_FLAG_ASSIGN_MASK)   // (vps_deposit_field's: silently ignored here, the caller would get the NN field)
     return vps_fail(ctx, VPS_ERR_ARG, "vps_nn_resample_quantity: VPS_FLAG_ASSIGN is taken by vps_deposit_field only (flags 0x%x)", flags);
   if (int rc = vps_check_weighted(ctx, "vps_nn_resample_quantity", quantity, flags)) return rc;

@@ -2,12 +2,16 @@
 // exponent of vps_set_density_weight -- and the two functions of rho that the density-weighted velocity and the scalar density
 // quantities are made of.  Shared by the brick / grid epilogues (deposit.hip), the NN emit (nn.hip) and the pencil kernel
 // (fft_pencil.h).  A new quantity starts here: its code in these five helpers, then its per-cell body in deposit.hip's cell_quantity.
-// (The velocity-gradient codes are no per-cell algebra: a stencil over a whole grid, gradient.hip -- vps_quantity_gradient.)
+// (The velocity-gradient codes are no per-cell algebra: a stencil over a whole grid, gradient.hip -- vps_quantity_gradient.
+//  Nor are the box-filter codes: sums over a box of cells of a whole grid, filter.hip -- vps_quantity_filter.)
 // Not part of the ABI.
 #pragma once
 #include "../../include/vps_hip.h"
 
-constexpr bool vps_quantity_valid(int q) { return q >= VPS_VELOCITY && q <= VPS_STRAIN_RATE; }
+// (15 is no code: include/vps_hip.h keeps it unassigned)
+constexpr bool vps_quantity_valid(int q) {
+  return (q >= VPS_VELOCITY && q <= VPS_STRAIN_RATE) || q == VPS_FILTERED_VM || q == VPS_FILTERED_STRESS;
+}
 // one output field, made from rho alone (channel 3 of [rho v, rho])
 constexpr bool vps_quantity_scalar_rho(int q) { return q == VPS_DENSITY || q == VPS_LOG_DENSITY; }
 // one output field that needs the second moment S2 = sum w rho_p |v_p|^2 next to the four cell totals: a fifth tile channel in
@@ -20,11 +24,15 @@ constexpr bool vps_quantity_second_moment(int q) { return q >= VPS_TOTAL_ENERGY 
 constexpr bool vps_quantity_tensor(int q) { return q == VPS_SUBGRID_STRESS || q == VPS_DISPERSION_TENSOR; }
 // fields of central differences of a gridded velocity (divergence: 1 field; vorticity: 3; strain rate: 6, in the tensor order):
 // a cell's value needs its six neighbours, which only a whole periodic grid of [v, mass] channels holds -- formed by
-// vps_field_algebra_out alone (gradient.hip), every other entry point refuses these codes (vps_refuse_gradient); no deposit, NN
+// vps_field_algebra_out alone (gradient.hip), every other entry point refuses these codes (vps_refuse_grid_only); no deposit, NN
 // or pencil kernel is instantiated for them (deposit.hip: dispatch_quantity does not know them)
 constexpr bool vps_quantity_gradient(int q) { return q >= VPS_DIVERGENCE && q <= VPS_STRAIN_RATE; }
+// box sums of a whole grid's [u, mass] channels at a half-width of VPS_FLAG_FILTER: the filtered [v, mass] grid (4 fields) and the
+// sub-filter stress (6, in the tensor order) -- formed by vps_field_algebra_out alone (filter.hip); refused everywhere else with
+// the gradient codes, and no deposit, NN or pencil kernel is instantiated for them
+constexpr bool vps_quantity_filter(int q) { return q == VPS_FILTERED_VM || q == VPS_FILTERED_STRESS; }
 constexpr int vps_quantity_channels(int q) {
-  return q == VPS_DIVERGENCE ? 1 : q == VPS_VORTICITY ? 3 : q == VPS_STRAIN_RATE ? 6 :
+  return q == VPS_FILTERED_VM ? 4 : q == VPS_FILTERED_STRESS ? 6 : q == VPS_DIVERGENCE ? 1 : q == VPS_VORTICITY ? 3 : q == VPS_STRAIN_RATE ? 6 :
          q == VPS_VM ? 4 : vps_quantity_tensor(q) ? 6 :
          (q == VPS_ENERGY || vps_quantity_scalar_rho(q) || vps_quantity_second_moment(q)) ? 1 : 3;
 }

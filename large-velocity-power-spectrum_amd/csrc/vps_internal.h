@@ -103,11 +103,19 @@ int vps_refuse_second_moment(vps_ctx* ctx, const char* who, int quantity, const 
 const char* vps_second_moment_name(int quantity);
 // The velocity-gradient quantities (VPS_DIVERGENCE, VPS_VORTICITY, VPS_STRAIN_RATE) are formed by vps_field_algebra_out alone,
 // from a whole grid; every other entry point that takes a quantity refuses them the same way.
-int vps_refuse_gradient(vps_ctx* ctx, const char* who, int quantity, const char* why);
+int vps_refuse_grid_only(vps_ctx* ctx, const char* who, int quantity, const char* why);
 const char* vps_gradient_name(int quantity);
 // gradient.hip: the stencil launch behind vps_field_algebra_out for those codes.  chans: [>= 3][N^3] velocity channels, out:
 // [vps_quantity_channels(quantity)][N^3], h = 1 / (2 Lcell) in float32; the caller has checked everything (N even, >= 4).
 void vps_gradient_launch(vps_ctx* ctx, int quantity, int N, float h, const float* chans, float* out);
+// The box-filter quantities (VPS_FILTERED_VM, VPS_FILTERED_STRESS) are formed by vps_field_algebra_out alone as well, and
+// vps_refuse_grid_only refuses them with the gradient codes: a box of cells is as little a per-cell quantity as a difference.
+const char* vps_filter_name(int quantity);
+// filter.hip: the launch behind vps_field_algebra_out for those codes.  chans: [4][N^3] = [u, mass], out:
+// [vps_quantity_channels(quantity)][N^3], half-width 1 <= m <= VPS_FILTER_MAX_HALF_WIDTH with 2m + 1 <= N,
+// c = 1 / (2m+1)^3 in float32; the caller has checked everything (N even, >= 4).
+#define VPS_FILTER_MAX_HALF_WIDTH 8   // what the kernel's LDS plan holds: a region of (16 + 2m) x (64 + 2m) cells, four channels
+void vps_filter_launch(vps_ctx* ctx, int quantity, int N, int m, float c, const float* chans, float* out);
 
 // Every entry point of the C ABI runs with the context's device current and restores the caller's
 // on return: the library allocates (tables, partial sums, lattice axes) and launches on streams

@@ -15,7 +15,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 CSRC = os.path.join(PKG_ROOT, "csrc")
 LIB_PATH = os.environ.get("VPS_LIB_PATH") or os.path.join(_HERE, "libvps_hip.so")  # override: experiments only
-SOURCES = ("api.hip", "deposit.hip", "gradient.hip", "nn.hip", "fft.hip", "fft_parts.hip", "hist.hip", "preprocess.hip", "comm.hip")
+SOURCES = ("api.hip", "deposit.hip", "gradient.hip", "filter.hip", "nn.hip", "fft.hip", "fft_parts.hip", "hist.hip", "preprocess.hip", "comm.hip")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics")
 
 # every symbol include/vps_hip.h declares: (name, restype, argtypes)

@@ -43,15 +43,30 @@ SECOND_MOMENT_QUANTITIES = {"total_energy": TOTAL_ENERGY, "subgrid_energy": SUBG
 # (BoxField.divergence / vorticity / strain_rate, HipKernels.velocity_gradient), not names the spectrum routes take.
 DIVERGENCE, VORTICITY, STRAIN_RATE = 12, 13, 14
 GRADIENT_QUANTITIES = {"divergence": DIVERGENCE, "vorticity": VORTICITY, "strain_rate": STRAIN_RATE}
+# the mass-weighted box filter of a WHOLE gridded field at a half-width of m cells (vps_field_algebra_out alone, csrc/filter.hip):
+# the filtered [v, mass] grid and the sub-filter stress (xx, yy, zz, xy, xz, yz).  15 stays unassigned (include/vps_hip.h).  Kept
+# OUT of QUANTITY like the gradient codes: spectra of a filtered field come through BoxField.filtered(m).
+FILTERED_VM, FILTERED_STRESS = 16, 17
+FILTER_QUANTITIES = {"vm": FILTERED_VM, "stress": FILTERED_STRESS}
+FILTER_MAX_HALF_WIDTH = 8          # what the kernel's LDS plan holds (csrc/vps_internal.h: VPS_FILTER_MAX_HALF_WIDTH)
 QUANTITY = {"velocity": VELOCITY, "momentum": MOMENTUM, "energy": ENERGY, "weighted_velocity": WEIGHTED,
             "density": DENSITY, "log_density": LOG_DENSITY, **SECOND_MOMENT_QUANTITIES}
 FLAG_REFERENCE_MOMENTUM_BUG = 1
 FLAG_INPUT_IS_VM = 2
 FLAG_REUSE_SORT = 4
 FLAG_SHARE_ENERGY = 8
+FLAG_FILTER_MASK = 0xfff000
+
+
+def FLAG_FILTER(m):
+    """VPS_FLAG_FILTER(m): the half-width m of the box filter (a box of (2m+1)^3 cells) in the flags of the two filter codes."""
+    return (int(m) & 0xfff) << 12
+
+
 NCOMP = {VELOCITY: 3, MOMENTUM: 3, ENERGY: 1, VM: 4, WEIGHTED: 3, DENSITY: 1, LOG_DENSITY: 1,      # output channels of a quantity
          TOTAL_ENERGY: 1, SUBGRID_ENERGY: 1, DISPERSION: 1,                                        # (csrc/quantity.h: vps_quantity_channels)
-         SUBGRID_STRESS: 6, DISPERSION_TENSOR: 6, DIVERGENCE: 1, VORTICITY: 3, STRAIN_RATE: 6}
+         SUBGRID_STRESS: 6, DISPERSION_TENSOR: 6, DIVERGENCE: 1, VORTICITY: 3, STRAIN_RATE: 6,
+         FILTERED_VM: 4, FILTERED_STRESS: 6}
 SCALAR_QUANTITIES = ("energy", "density", "log_density", "total_energy", "subgrid_energy", "dispersion")      # one field each: dealt out and transformed as one unit
 
 
@@ -712,6 +727,38 @@ class HipKernels:
         elif tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError("velocity_gradient: out must be a contiguous %s tensor" % (shape,))
         self._chk(self.lib.vps_field_algebra_out(self.ctx, code, FLAG_INPUT_IS_VM, float(Lcell),
+                                                 self._ptr(chans, torch.float32), N ** 3, self._ptr(out, torch.float32)))
+        return out
+
+    def box_filter(self, chans, N, half_width, what="vm", out=None):
+        """Mass-weighted box filter of a whole periodic grid (vps_field_algebra_out, csrc/filter.hip): chans [4, N, N, N] float32 =
+        vx, vy, vz, mass, a box of (2 half_width + 1)^3 cells around every cell, every index wrapped.  what 'vm' (or 16) ->
+        [4, N, N, N]: the Favre-filtered velocity sum(mass v) / sum(mass) (0 where the box holds no mass) and the filtered mass
+        sum(mass) / (2m+1)^3, again [v, mass] channels; 'stress' (or 17) -> [6, N, N, N]: the sub-filter stress
+        (sum(mass v_i v_j) - sum(mass v_i) sum(mass v_j) / sum(mass)) / (2m+1)^3 in the order xx, yy, zz, xy, xz, yz.  `out`: a
+        tensor of that shape to write into; it must not overlap `chans`."""
+        code = FILTER_QUANTITIES.get(what, what) if isinstance(what, str) else int(what)
+        if code not in FILTER_QUANTITIES.values():
+            raise ValueError("box_filter forms %s, not %r" % (" | ".join(repr(n) for n in FILTER_QUANTITIES), what))
+        N = int(N)
+        if tuple(chans.shape) != (4, N, N, N):
+            raise ValueError("box_filter needs the [4, N, N, N] channels of a whole grid, got %s for N = %d"
+                             % (tuple(chans.shape), N))
+        if N < 4 or N % 2:
+            raise ValueError("box_filter needs an even N >= 4, got %d" % N)
+        if half_width != int(half_width) or not 1 <= int(half_width) <= FILTER_MAX_HALF_WIDTH:
+            raise ValueError("box_filter: the half-width is a whole number of cells from 1 to %d, got %r"
+                             % (FILTER_MAX_HALF_WIDTH, half_width))
+        m = int(half_width)
+        if 2 * m + 1 > N:
+            raise ValueError("box_filter: the box of 2 * %d + 1 cells is wider than the grid (N = %d)" % (m, N))
+        self._stream()
+        shape = (NCOMP[code], N, N, N)
+        if out is None:
+            out = self.empty(shape, torch.float32)
+        elif tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError("box_filter: out must be a contiguous %s tensor" % (shape,))
+        self._chk(self.lib.vps_field_algebra_out(self.ctx, code, FLAG_INPUT_IS_VM | FLAG_FILTER(m), 1.0,
                                                  self._ptr(chans, torch.float32), N ** 3, self._ptr(out, torch.float32)))
         return out
 
