@@ -14,6 +14,16 @@ NCH = {"divergence": 1, "vorticity": 3, "strain_rate": 6}
 TENSOR_ORDER = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))          # xx, yy, zz, xy, xz, yz
 
 
+def layout(N, num_cu=256):
+    """(xchunk, vec) of the launch of csrc/gradient.hip (gradient_launch_q): 16-byte groups of 4 cells where N % 4 == 0, else 2;
+    tiles of 16 rows by 16 groups; enough x chunks for 16 workgroups per CU, but chunks of no less than 64 planes where N allows
+    -- unlike the filter's (filter_ref.layout) a chunk has no longest length."""
+    vec = 4 if N % 4 == 0 else 2
+    tiles = -(-N // (16 * vec)) * -(-N // 16)
+    nxc = max(1, min(-(-16 * num_cu // tiles), N // 64))
+    return -(-N // nxc), vec
+
+
 def derivatives64(u, Lcell):
     """d[c][a] = d u_c / d x_a, float64."""
     u = np.asarray(u, dtype=np.float64)
